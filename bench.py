@@ -8,9 +8,15 @@ gradient all-reduce -> Adam) at 256x512, N=49, batch 8 per GPU, synthetic data, 
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `value` = stereo pairs/s over all ranks with inputs resident in HBM.
-`roofline` = the dominant kernel's achieved rate (algorithmic FLOPs / HIP-event time, from an instrumented
-pass after the timed region).  `cpu_baseline` = the CPU oracle (oracle/falnet_oracle.py: a torch-CPU
-restatement of the same step) timed on this host on a bounded sample -- the only use of oracle/ here.
+A plain run only sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR` also writes what
+the last timed step computed, see dump_outputs).  The last timed step starts from the benchmark's seeded starting
+state again (StartState), so that its inputs, and what it computes from them, are the same in every run.
+`--full` adds the legs after the timed region, each of which the `--no-*` switches can still leave out:
+`roofline` = the dominant kernel's achieved rate (algorithmic FLOPs / HIP-event time, from an instrumented pass)
+with live HBM-traffic passes and the sustained MFMA rate;
+`cpu_baseline` = the CPU oracle (oracle/falnet_oracle.py: a torch-CPU restatement of the same step) timed on
+this host on a bounded sample -- the only use of oracle/ here -- with `abs_rel_vs_ref` and `abs_rel_vs_gt`;
+`allreduce` (N > 1) = the collective measured on its own; `host_issue_ms_per_step` from an idle device.
 """
 import argparse
 import json
@@ -379,6 +385,60 @@ def allreduce_report(model, step, args, world, rank, dev, ms_per_step):
             "isolated_vs_ring_bound": (ring_ms / iso["whole_buffer"]) if iso["whole_buffer"] > 0 else None}
 
 
+class StartState:
+    """The benchmark's starting state -- seeded weights, no Adam moments, step count 0, the initial loss scale (f16) -- taken before the first
+    step, and put back right before the LAST timed step.  The steps before it train as before, but their f32 atomics (split-K, the reductions)
+    sum in a different order in every run and the Adam steps amplify that rounding: the weights after a few dozen steps differ from run to run
+    by far more than rounding.  One step from this state computes the same outputs in every run up to rounding (--dump-outputs writes them).
+    The restore is queued on the current stream, like a step; main() takes its device time out of the timed region."""
+
+    def __init__(self, model):
+        from fal_net_amd import train
+        self.flat = model.ensure_flat().detach().clone()
+        sc = train.loss_scaler(model)
+        self.scale = None if sc is None else sc.state.clone()
+
+    def restore(self, model, opt):
+        from fal_net_amd import train
+        model.flat_parameters().copy_(self.flat)
+        model.mark_weights_changed()
+        if opt.m is not None:
+            opt.m.zero_()
+            opt.v.zero_()
+            opt.state[1:].zero_()  # device-resident step count (bias correction)
+        opt.t = 0
+        if self.scale is not None:
+            train.loss_scaler(model).state.copy_(self.scale)
+        model.repack_after_optimizer()  # the compute-dtype copies of the restored weights, now rather than inside the step
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # all arrays together, .npy headers aside: inside 64 MB
+
+
+def dump_outputs(path, out, model):
+    """`--dump-outputs DIR`: what the timed path gave its caller in the LAST timed step -- every array of the step's result dict
+    (loss terms, synthesised view, disparities, ...) and the model state after it (flat parameters and gradients) -- as
+    DIR/<name>.npy in float32.  Each array gets an equal share of DUMP_BUDGET_BYTES; a larger one is written as a fixed sample of its
+    flattened elements (sorted indices drawn with seed 0 from its size alone: the same elements in every run of the same arguments).
+    Called right after the timed loop: the result dict aliases the plan's buffers, which the next step overwrites."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().float().cpu().numpy()
+        elif isinstance(v, (int, float)):
+            arrays[k] = np.asarray(v, dtype=np.float32)
+    arrays["parameters"] = model.flat_parameters().detach().float().cpu().numpy()
+    arrays["gradients"] = model.flat_gradients().detach().float().cpu().numpy()
+    cap = DUMP_BUDGET_BYTES // (4 * len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        a = a.astype(np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port <free> bench.py <same arguments>` as a child process and return its exit code.  Lines are relayed as they come; a JSON result line
@@ -421,6 +481,11 @@ def main():
                     help="stage1: BASELINE configs[1] (default); stage2: configs[3] (Train_Stage2_K.py:233-331, teacher = copy of the "
                          "student); highres: configs[4] (Stage-1 step at 384x1280, N=96, f16 unless --dtype says otherwise)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "f16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the measurement legs of the module docstring (roofline, CPU baseline, parity, trajectory, "
+                         "N > 1 all-reduce report, idle-device issue time); off by default: a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-trajectory", action="store_true", help="skip the abs_rel_vs_gt leg (200 training steps per dtype on structured stereo, ~15 s)")
@@ -428,8 +493,10 @@ def main():
                     help="roofline.traffic from the committed profiles/ file instead of two live rocprofv3 --pmc child passes (~25 s each)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one captured hipGraph (measured slower than eager launches on ROCm 7.0: off by default)")
-    ap.add_argument("--launch-table", default=None, help="write the per-launch time table of the instrumented pass here")
+    ap.add_argument("--launch-table", default=None, help="write the per-launch time table of the instrumented pass here (with --full)")
     args = ap.parse_args()
+    if args.launch_table and not (args.full and not args.no_roofline):
+        ap.error("--launch-table is written by the instrumented pass: give --full (and not --no-roofline)")
     if args.workload == "highres":
         args.height, args.width, args.levels = 384, 1280, 96
     if args.dtype is None:
@@ -483,6 +550,7 @@ def main():
     opt = train.FlatAdam(model, lr=1e-4, betas=(0.5, 0.999))
     left, right, mn, mx = synthetic.synthetic_pair(args.batch, args.height, args.width, seed=1234 + rank)
     left, right, mx = left.to(dev), right.to(dev), mx.to(dev)  # inputs resident in HBM before the timed region
+    start = StartState(model)
 
     fix_model = None
     if args.workload == "stage2":  # frozen Stage-1 teacher (Train_Stage2_K.py:190-198): here a copy of the student's weights
@@ -515,10 +583,17 @@ def main():
     # one event per 10 steps on the step's stream (no synchronisation inside the timed loop): min / median / max of the 10-step windows show the
     # box's jitter in the line itself
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps // 10 + 1)] if not graphed else []
+    restore = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         if marks and i % 10 == 0:
             marks[i // 10].record()
+        if i == args.steps - 1:  # the last timed step starts from the seeded state (StartState), bracketed by events -- also after the
+            # steps a graphed run takes while it captures, hence whatever ran before
+            restore = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            restore[0].record()
+            start.restore(model, opt)
+            restore[1].record()
         out = step()
     if marks and args.steps % 10 == 0:
         marks[-1].record()
@@ -526,24 +601,30 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    restore_ms = restore[0].elapsed_time(restore[1]) if restore else 0.0
+    elapsed = time.perf_counter() - t0 - restore_ms * 1e-3  # the steps alone: the restore's device time is not a step's
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss = float(out["loss"])
-    # host time to ISSUE a step, measured where the queues cannot push back: three steps from an idle device (inside the timed loop a
-    # host that runs ahead blocks on the hardware queues, and `issued` then measures the GPU, not the host)
-    torch.cuda.synchronize()
-    ti = time.perf_counter()
-    for _ in range(3):
-        step()
-    issue_idle = (time.perf_counter() - ti) / 3
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
+    issue_idle = None
+    if args.full:
+        # host time to ISSUE a step, measured where the queues cannot push back: three steps from an idle device (inside the timed loop a
+        # host that runs ahead blocks on the hardware queues, and `issued` then measures the GPU, not the host)
+        torch.cuda.synchronize()
+        ti = time.perf_counter()
+        for _ in range(3):
+            step()
+        issue_idle = (time.perf_counter() - ti) / 3
+        torch.cuda.synchronize()
     ms = elapsed * 1e3 / args.steps
     pairs_per_s = world * args.batch * args.steps / elapsed
     nwin = args.steps // 10 if marks else 0
-    wins = sorted(marks[k].elapsed_time(marks[k + 1]) / 10 for k in range(nwin if args.steps % 10 == 0 else max(nwin - 1, 0))) if nwin else []
+    wins = sorted((marks[k].elapsed_time(marks[k + 1]) - (restore_ms if k == (args.steps - 1) // 10 else 0.0)) / 10
+                  for k in range(nwin if args.steps % 10 == 0 else max(nwin - 1, 0))) if nwin else []
 
     stage = "Stage-2" if args.workload == "stage2" else "Stage-1"
     cfg_name = {"stage1": "BASELINE configs[1]", "stage2": "BASELINE configs[3] on one GPU", "highres": "BASELINE configs[4] on one GPU"}[args.workload]
@@ -557,8 +638,11 @@ def main():
                    "global_batch": world * args.batch, "parallelism": f"dp{world}", "final_loss": loss,
                    "launch": "hipGraph replay" if graphed else ("eager launches, recorded sequences issued by falnet_replay (C)" if os.environ.get("FALNET_REPLAY", "1") == "1"
                                                                        else "eager launches from Python"),
-                   "host_issue_ms_per_step": issue_idle * 1e3, "host_issue_ms_per_step_in_timed_loop": issued * 1e3 / args.steps},
+                   "host_issue_ms_per_step_in_timed_loop": issued * 1e3 / args.steps,
+                   "last_step_restore_ms": restore_ms},  # device time of StartState.restore, taken out of the timed region
     }
+    if issue_idle is not None:
+        result["config"]["host_issue_ms_per_step"] = issue_idle * 1e3
     st_plan = next((p for p in getattr(model, "_plans", {}).values() if getattr(p, "selftest", None)), None)
     if st_plan is not None:  # stream / hardware-queue self-test of the step's streams (plan.stream_selftest)
         t = st_plan.selftest
@@ -569,9 +653,9 @@ def main():
         result["ms_per_step_10step_windows"] = {"min": round(wins[0], 4), "median": round(wins[len(wins) // 2], 4), "max": round(wins[-1], 4), "n": len(wins),
                                                 "source": "HIP events on the step's stream every 10 steps inside the timed region (rank 0's device)"}
 
-    if world > 1 or os.environ.get("FALNET_FORCE_DIST") == "1":
+    if args.full and (world > 1 or os.environ.get("FALNET_FORCE_DIST") == "1"):
         result["allreduce"] = allreduce_report(model, eager_step, args, world, rank, dev, ms)
-    if world > 1:
+    if args.full and world > 1:
         # Everything below runs on rank 0 ONLY (phase marks, the instrumented pass): steps issued there must not issue collectives the other ranks
         # never join -- they would wait for their peers forever.  The timed region and the all-reduce report are done; from here on the bucket
         # hooks and allreduce_gradients skip the collective on every rank (the weights may diverge now: nothing below compares them).
@@ -579,7 +663,7 @@ def main():
         dist.barrier()
 
     phase_ms = None
-    if rank == 0 and not args.no_roofline and args.workload != "stage2" and not graphed:
+    if args.full and rank == 0 and not args.no_roofline and args.workload != "stage2" and not graphed:
         # phase boundaries of the REAL step (all streams live, replayed launch sequences): five HIP events per step on the step's stream, 10 steps,
         # NOT part of the timed region.  With the per-phase algorithmic FLOPs of the instrumented pass below this is `roofline.phase_tflops`:
         # where the step delivers its FLOPs and where it does not, without a trace.
@@ -591,7 +675,7 @@ def main():
         if train.PHASE_MARKS and all(len(m) == 5 for m in train.PHASE_MARKS):
             phase_ms = {n: sorted(m[i].elapsed_time(m[i + 1]) for m in train.PHASE_MARKS)[len(train.PHASE_MARKS) // 2] for i, n in enumerate(names)}
         train.PHASE_MARKS = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # instrumented pass (NOT part of the timed region): HIP events around every launch
         timer = EventTimer()
         ops.TIMER = timer
@@ -665,10 +749,10 @@ def main():
             result["roofline"]["med_head_hbm"] = {"bound": "hbm", "achieved": hb / (hms * 1e-3) / 1e9, "peak": 8000.0,
                                                   "unit": "GB/s", "frac": hb / (hms * 1e-3) / 1e9 / 8000.0, "ms_per_step": hms}
         result["kernel_breakdown_ms_per_step"] = {t: round(a["ms"] / 3, 4) for t, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.workload, args.height, args.width, args.levels)
         result["abs_rel_vs_ref"] = parity_vs_oracle(args.height, args.width, args.levels, dev)
-    if rank == 0 and world == 1 and args.workload == "stage1" and not args.no_trajectory and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.workload == "stage1" and not args.no_trajectory and not args.no_cpu_baseline:
         result["abs_rel_vs_gt"] = abs_rel_vs_ground_truth(args)
     if dist.is_initialized():
         dist.destroy_process_group()

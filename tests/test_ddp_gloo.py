@@ -2,6 +2,7 @@
 1/world scale folded into the optimiser -- reproduces single-process gradients of the concatenated batch."""
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -170,3 +171,49 @@ def test_bench_gpus_mismatch_is_refused():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", FALNET_BENCH_DRYRUN="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+
+
+def test_bench_launch_table_needs_full():
+    """The per-launch table comes from the instrumented pass, a leg of --full: asked for without it, bench.py refuses before any GPU call."""
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--launch-table", os.devnull], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.dump_outputs on host tensors shaped like a step's result: every array as float32 .npy, 64 MB at most in all (the two flat
+    buffers alone are 96 MB here), a large array as the same seeded sample of its elements in every run."""
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    prog = """
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+import bench
+class M:
+    def flat_parameters(self):
+        return torch.arange(12000000, dtype=torch.float32)
+    def flat_gradients(self):
+        return -torch.arange(12000000, dtype=torch.float32)
+out = {"loss": torch.tensor(1.5), "sm": 0, "ldisp": torch.rand(8, 1, 256, 512, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16),
+       "scaler": None}
+bench.dump_outputs(sys.argv[2], out, M())
+"""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"d{i}"
+        r = subprocess.run([sys.executable, "-c", prog, root, str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert sorted(f.name for f in d.iterdir()) == ["gradients.npy", "ldisp.npy", "loss.npy", "parameters.npy", "sm.npy"]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64e6
+        dumps.append({f.name: np.load(f) for f in d.iterdir()})
+    a, b = dumps
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert float(a["loss.npy"]) == 1.5 and float(a["sm.npy"]) == 0.0
+    p = a["parameters.npy"]
+    assert p.ndim == 1 and 1000 < p.size < 12000000 and np.all(np.diff(p) > 0)  # sorted indices, no repeats: p holds the indices themselves (exact in f32 below 2**24)
+    assert np.array_equal(a["gradients.npy"], -p)  # the same elements of both flat buffers
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

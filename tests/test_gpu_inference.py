@@ -62,7 +62,7 @@ def test_checkpoint_roundtrip_reference_format(tmp_path):
     ["Train_Stage2_K.py", "-mm", "FAL_netA", "--synthetic", "--epochs", "1", "--epoch_size", "2", "-b", "1", "-ch", "64", "-cw", "128", "-p", "1", "-no_levels", "7"],
 ])
 def test_entry_scripts_synthetic(cmd, tmp_path):
-    extra = ["--save-path", str(tmp_path)] if cmd[0].startswith("Train_Stage1_K") else []
+    extra = ["--save-path", str(tmp_path)] if cmd[0].startswith("Train_") else []  # (not the repository: a Train_* run saves its checkpoints)
     r = subprocess.run([sys.executable, os.path.join(ROOT, cmd[0])] + cmd[1:] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "{" in r.stdout

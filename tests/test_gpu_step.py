@@ -266,19 +266,108 @@ def test_16bit_steps_run_and_track_f32():
 
 def test_collective_path_world1(tmp_path):
     """The N>1 code path on one GPU: RCCL process group of size 1, bucketed asynchronous all-reduce behind backward,
-    1/world folded into Adam -- the step must reproduce the single-process result."""
+    1/world folded into Adam -- the step must reproduce the single-process result.  bench.py's last timed step starts from the seeded
+    state in both runs, so what it computes THROUGH the collective is compared (its --dump-outputs): the all-reduced gradients and the
+    weights after Adam, besides the losses and forward outputs -- to the reordering of f32 atomics, and Adam's +-lr on sign-unstable
+    near-zero gradients (the tolerances of test_overlapped_allreduce_equals_single_allreduce_world1)."""
     import subprocess, sys, json
     env = dict(os.environ, FALNET_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29517", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    outs = []
-    for e in (env, dict(os.environ)):
+    outs, dumps = [], []
+    for name, e in (("dist", env), ("single", dict(os.environ))):
+        d = tmp_path / name
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--height", "64",
-                            "--width", "128", "--no-cpu-baseline", "--no-roofline", "--dtype", "f32"], capture_output=True, text=True, env=e, timeout=600)
+                            "--width", "128", "--no-cpu-baseline", "--no-roofline", "--dtype", "f32", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=e, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
         assert r.stdout.strip().splitlines()[-1] == line  # the JSON is the last line even with RCCL's banner
         outs.append(json.loads(line)["config"]["final_loss"])
+        dumps.append({f.name: np.load(f).astype(np.float64) for f in sorted(d.iterdir())})
     assert abs(outs[0] - outs[1]) < 1e-5 * abs(outs[1]), outs
+    a, b = dumps
+    assert a.keys() == b.keys() and {"gradients.npy", "parameters.npy"} <= set(a)
+    for k in ("loss.npy", "rec.npy", "sm.npy"):
+        assert rel(a[k], b[k]) < 1e-5, k
+    for k in ("ldisp.npy", "rpan.npy"):
+        assert rel(a[k], b[k]) < TOL, k
+    assert rel(a["gradients.npy"], b["gradients.npy"]) < 2e-3
+    dp = np.abs(a["parameters.npy"] - b["parameters.npy"])
+    assert dp.max() <= 2.1e-4 and np.mean(dp > 1e-6) < 0.05  # one Adam step of lr = 1e-4: at most a flipped +-lr, on few elements
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and reports them without any leg of --full; `--dump-outputs` writes what
+    the last timed step computed as float32 .npy files within 64 MB, its loss the line's final_loss.  Same arguments, same inputs: two runs in
+    deterministic mode dump identical arrays."""
+    import subprocess, sys, json
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = dict(os.environ, FALNET_DETERMINISTIC="1")
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--height", "64", "--width", "128", "--dtype", "f32", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64e6
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    for leg in ("roofline", "cpu_baseline", "abs_rel_vs_ref", "abs_rel_vs_gt", "allreduce", "kernel_breakdown_ms_per_step"):
+        assert leg not in line, leg
+    a, b = dumps
+    assert {"loss.npy", "ldisp.npy", "rpan.npy", "parameters.npy", "gradients.npy"} <= set(a) and a.keys() == b.keys()
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert abs(float(a["loss.npy"]) - line["config"]["final_loss"]) <= 1e-6 * abs(line["config"]["final_loss"])
+    assert a["ldisp.npy"].shape == (2, 1, 64, 128) and np.isfinite(a["ldisp.npy"]).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def _bench_dump(tmp_path, name, args, env=None, small=True):
+    import subprocess, sys, json
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    d = tmp_path / name
+    size = ["--batch", "2", "--height", "64", "--width", "128"] if small else []
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + size + ["--dump-outputs", str(d)] + args,
+                       capture_output=True, text=True, env=dict(os.environ, **(env or {})), timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1]), {f.name: np.load(f) for f in sorted(d.iterdir())}
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_bench_last_step_starts_from_seeded_state(dtype, tmp_path):
+    """The last timed step of bench.py starts from the seeded starting state again (bench.StartState: weights and their packed copies, Adam
+    moments, step count, f16 loss scale): in deterministic mode its outputs after warm-up and earlier timed steps are bit-identical to those
+    of a run whose only step is the first one."""
+    det = {"FALNET_DETERMINISTIC": "1"}
+    line_r, restored = _bench_dump(tmp_path, "restored", ["--steps", "4", "--warmup", "2", "--dtype", dtype], det)
+    line_f, first = _bench_dump(tmp_path, "first", ["--steps", "1", "--warmup", "0", "--dtype", dtype], det)
+    assert line_r["steps"] == 4 and line_f["steps"] == 1
+    assert restored.keys() == first.keys()
+    for k in restored:
+        assert np.array_equal(restored[k], first[k]), k
+
+
+def test_bench_dumps_repeat_in_default_mode(tmp_path):
+    """Two runs of the same plain bench.py arguments at the benchmark's own configuration (its kernel choices replayed from the committed
+    autotune cache), default (non-deterministic) mode: the f32 atomics of the step round differently in every run, but the last step computes
+    from the same inputs, so its outputs agree up to that rounding -- the forward outputs and losses to 1e-3, the gradients to 1e-2 of their
+    largest element, the weights after Adam's first step to the +-lr of a sign flip of a gradient that rounds across zero, on few elements.
+    (Without the restore the losses of two runs differ by several per cent and nearly every weight differs.)"""
+    args = ["--steps", "12", "--warmup", "3"]
+    (la, a), (lb, b) = _bench_dump(tmp_path, "a", args, small=False), _bench_dump(tmp_path, "b", args, small=False)
+    assert a.keys() == b.keys()
+    rel = lambda x, y: float(np.abs(x.astype(np.float64) - y).max() / max(np.abs(y).max(), 1e-30))
+    for k in ("loss.npy", "rec.npy", "sm.npy", "ldisp.npy", "rpan.npy"):
+        assert rel(a[k], b[k]) < 1e-3, k
+    assert abs(la["config"]["final_loss"] - lb["config"]["final_loss"]) < 1e-3 * abs(lb["config"]["final_loss"])
+    assert rel(a["gradients.npy"], b["gradients.npy"]) < 1e-2
+    dp = np.abs(a["parameters.npy"].astype(np.float64) - b["parameters.npy"])
+    assert dp.max() <= 2e-4 + 1e-6 and np.mean(dp > 1e-6) < 0.1
 
 
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
@@ -593,7 +682,7 @@ def test_bench_two_ranks_reports_allreduce(launch):
     head = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541"] \
         if launch == "torchrun" else [sys.executable]
     cmd = head + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "128",
-           "--no-cpu-baseline", "--dtype", "f32"] + (["--no-roofline"] if launch == "torchrun" else ["--no-live-traffic"])
+           "--full", "--no-cpu-baseline", "--dtype", "f32"] + (["--no-roofline"] if launch == "torchrun" else ["--no-live-traffic"])
     # (the self-launched form runs rank 0's measurement legs too -- phase marks, the instrumented pass: steps on ONE rank after the timed region, which
     #  must not issue collectives the other rank never joins)
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200)

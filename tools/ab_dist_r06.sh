@@ -2,6 +2,7 @@
 # same-box A/B of the data-parallel step's collective placement (run on the GPU box): single GPU vs world-1 RCCL group with the bucket all-reduces
 # on the backend's own stream (FALNET_COMM_ON_AUX=0, rounds 4-5) vs as sync collectives on the auxiliary stream (default, round 6)
 out=gpurun_out/r06_ab_dist.txt
+logs=$(dirname "$out")
 : > $out
 line() { python3 - "$1" "$2" <<'PY'
 import json,sys
@@ -12,8 +13,8 @@ print(sys.argv[2], round(d['value'],1), round(d['ms_per_step'],3), 'exposed_ms',
 PY
 }
 for r in 1 2 3; do
-  python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-roofline --no-trajectory > gpurun_out/_s.log 2>&1; line gpurun_out/_s.log "single" >> $out
-  FALNET_FORCE_DIST=1 python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-roofline --no-trajectory > gpurun_out/_d1.log 2>&1; line gpurun_out/_d1.log "world-1 RCCL, collectives on aux (default)" >> $out
-  FALNET_AB=1 FALNET_COMM_ON_AUX=0 FALNET_FORCE_DIST=1 python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-roofline --no-trajectory > gpurun_out/_d0.log 2>&1; line gpurun_out/_d0.log "world-1 RCCL, collectives on the backend's stream (r5)" >> $out
+  python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-roofline --no-trajectory > $logs/_s.log 2>&1; line $logs/_s.log "single" >> $out
+  FALNET_FORCE_DIST=1 python3 bench.py --steps 40 --warmup 10 --full --no-cpu-baseline --no-roofline --no-trajectory > $logs/_d1.log 2>&1; line $logs/_d1.log "world-1 RCCL, collectives on aux (default)" >> $out
+  FALNET_AB=1 FALNET_COMM_ON_AUX=0 FALNET_FORCE_DIST=1 python3 bench.py --steps 40 --warmup 10 --full --no-cpu-baseline --no-roofline --no-trajectory > $logs/_d0.log 2>&1; line $logs/_d0.log "world-1 RCCL, collectives on the backend's stream (r5)" >> $out
 done
 cat $out
