@@ -103,7 +103,7 @@ def backbone_forward(sd, x, flow):
 # --------------------------------------------------------------------------- MED head
 def plane_disparities(min_disp, max_disp, n_planes):
     """d_n = max*exp(ln(max/min)*(n/(N-1)-1)), per sample (FAL_netB.py:223-225). -> (B,N)."""
-    c = torch.arange(n_planes, dtype=torch.float32) / (n_planes - 1)
+    c = torch.arange(n_planes, dtype=max_disp.dtype) / (n_planes - 1)  # follows the inputs' dtype (float64 oracle runs)
     mx, mn = max_disp.reshape(-1, 1), min_disp.reshape(-1, 1)
     return mx * torch.exp(torch.log(mx / mn) * (c.view(1, -1) - 1.0))
 
@@ -138,7 +138,7 @@ def _maskr_align_corners_false(sm, d):
     with align_corners=True (:231,:241-242): pixel (x, y) reads (x*W/(W-1) + d_n - 0.5, y*H/(H-1) - 0.5), bilinear in both
     axes with zero padding.  Restated with torch's own grid_sample (torch is the oracle for that arithmetic)."""
     B, N, H, W = sm.shape
-    th = torch.zeros(B, 2, 3)
+    th = torch.zeros(B, 2, 3, dtype=sm.dtype)
     th[:, 0, 0] = 1
     th[:, 1, 1] = 1
     grid = F.affine_grid(th, [B, 1, H, W], align_corners=True)
@@ -239,7 +239,7 @@ def rec_loss_fnc(vsd, mask, synth, label, vgg_label, a_p):
 def smoothness(img, disp, gamma=1):
     """Edge-aware smoothness, loss_functions.py:70-101 (+ getGrayscale :104-109).
     Zero padding 1 is applied to the already-cropped tensors (conv2d padding=1)."""
-    mean = torch.tensor([0.411, 0.432, 0.45]).view(1, 3, 1, 1)
+    mean = torch.tensor([0.411, 0.432, 0.45], dtype=img.dtype).view(1, 3, 1, 1)
     rgb = img + mean
     g = (0.299 * rgb[:, 0] + 0.587 * rgb[:, 1] + 0.114 * rgb[:, 2]).unsqueeze(1).detach()
     gp = F.pad(g, (1, 1, 1, 1))

@@ -19,6 +19,8 @@ from fal_net_amd import synthetic, train  # noqa: E402
 from fal_net_amd.models import FAL_netB  # noqa: E402
 from oracle import falnet_oracle as O  # noqa: E402
 
+from _grad_parity import grad_parity  # noqa: E402
+
 DEV = "cuda"
 TOL = 1e-4
 B, H, W, N = 8, 256, 512, 49
@@ -55,6 +57,45 @@ def _f32_stage1():
     if "s1" not in _F32:
         _F32["s1"] = _stage1(torch.float32)
     return _F32["s1"]
+
+
+_O64 = {}
+
+
+def _oracle64(shape, stage2=False, chunk=2):
+    """The oracle's step on the inputs of _stage1 / _stage2 in FLOAT64 (weights, VGG, images): no f32 summation noise on the reference side.
+    Run in chunks of `chunk` samples: every loss term is a batch mean, so the losses are averaged and the gradients summed with the chunk's
+    share of the batch as weight.  Computed once per module and shape."""
+    key = ("s2" if stage2 else "s1",) + tuple(shape)
+    if key in _O64:
+        return _O64[key]
+    b, h, w, n = shape
+    left, right, mn, mx = (t.double() for t in synthetic.synthetic_pair(b, h, w, seed=1234))
+    sd = {k: v.double() for k, v in synthetic.seeded_falnetb_state_dict(n).items()}
+    vsd = {k: v.double() for k, v in synthetic.seeded_vgg19_state_dict().items()}
+    params = O.leaf_params(sd)
+    torch.set_num_threads(min(32, torch.get_num_threads()))
+    names = ("loss", "rec", "sm", "mirror") if stage2 else ("loss", "rec", "sm")
+    maps = ("ldisp", "rdisp", "O_L", "O_R") if stage2 else ("ldisp", "rpan")
+    res = {k: 0.0 for k in names}
+    parts = {k: [] for k in maps}
+    for i in range(0, b, chunk):
+        sl = slice(i, min(b, i + chunk))
+        wgt = (sl.stop - sl.start) / b
+        if stage2:
+            out = O.stage2_losses(params, sd, vsd, left[sl], right[sl], mn[sl], mx[sl])
+        else:
+            out = O.stage1_losses(params, vsd, left[sl], right[sl], mn[sl], mx[sl])
+        (out["loss"] * wgt).backward()
+        for k in names:
+            res[k] += float(out[k]) * wgt
+        for k in maps:
+            parts[k].append(out[k].detach())
+        del out
+    res.update({k: torch.cat(v, 0) for k, v in parts.items()})
+    res["grads"] = {k: p.grad.detach().clone() for k, p in params.items() if p.grad is not None}
+    _O64[key] = res
+    return res
 
 
 def _f32_det(shape, tmp_path_factory, stage2=False):
@@ -98,13 +139,23 @@ def _compare_16bit(ref, got, dt, what, loss_tol=2e-2, disp_tol=None):
     return rows
 
 
+def _compare_16bit_vs_oracle(oref, got, dt, what):
+    """The same per-tensor bounds (NORM_TOL / COS_MIN) against the float64 oracle's gradients of the same inputs."""
+    bad, worst = [], ("", 0.0, 1.0)
+    for k, g in got["grads"].items():
+        r = oref["grads"][k].double().reshape(-1)
+        g = g.double().reshape(-1)
+        nd = abs(float(g.norm()) - float(r.norm())) / float(r.norm())
+        cos = float(torch.nn.functional.cosine_similarity(g, r, dim=0))
+        worst = (k, max(worst[1], nd), min(worst[2], cos))
+        if nd > NORM_TOL[dt] or cos < COS_MIN:
+            bad.append((k, nd, cos))
+    print(f"{what} {dt} vs float64 oracle: worst grad-norm dev {worst[1]:.2e}, worst per-tensor cosine {worst[2]:.6f}")
+    assert not bad, bad
+
+
 def _check_vs_oracle(hip, shape, what):
-    b, h, w, n = shape
-    left, right, mn, mx = synthetic.synthetic_pair(b, h, w, seed=1234)
-    sd = synthetic.seeded_falnetb_state_dict(n)
-    params = O.leaf_params(sd)
-    torch.set_num_threads(min(32, torch.get_num_threads()))
-    ref = O.stage1_step(params, O.OracleAdam(params), synthetic.seeded_vgg19_state_dict(), left, right, mn, mx)  # gradients in ref["grads"]
+    ref = _oracle64(shape, chunk=1 if shape[1] * shape[2] > H * W else 2)  # float64, gradients summed over chunks of the batch
     for k in ("loss", "rec", "sm"):
         assert abs(hip[k] - float(ref[k])) / abs(float(ref[k])) < TOL, (k, hip[k], float(ref[k]))
     assert rel(hip["ldisp"], ref["ldisp"]) < TOL
@@ -117,12 +168,14 @@ def _check_vs_oracle(hip, shape, what):
         e = abs(gn - float(g.norm())) / float(g.norm())
         worst = max(worst, (k, e), key=lambda t: t[1])
         assert e < 2e-3, (k, gn, float(g.norm()))
-    print(what, "f32 vs oracle: worst gradient-norm deviation", worst)
+    print(what, "f32 vs float64 oracle: worst gradient-norm deviation", worst)
+    # element-wise: a norm is blind to swapped taps, flipped signs, permuted channels, misplaced tiles
+    grad_parity({k: g for k, g in hip["grads"].items() if k in ref["grads"]}, ref["grads"], norm_tol=2e-3, what=f"{what} f32")
 
 
 def test_stage1_b8_f32_vs_oracle():
-    """One Stage-1 step at B=8, 256x512, N=49 in f32 against the CPU oracle: loss scalars and disparity 1e-4, synthesised view
-    2e-4 (the reference's own fp32 grid noise), every parameter's gradient norm 2e-3."""
+    """One Stage-1 step at B=8, 256x512, N=49 in f32 against the float64 CPU oracle: loss scalars and disparity 1e-4, synthesised view
+    2e-4 (the reference's own fp32 grid noise), every parameter's gradient norm 2e-3 and element-wise (grad_parity)."""
     _check_vs_oracle(_f32_stage1(), (B, H, W, N), "B=8 256x512 N=49")
 
 
@@ -144,13 +197,22 @@ def test_highres_b1_f32_step_vs_oracle():
     _check_vs_oracle(_stage1(torch.float32, shape), shape, "B=1 384x1280 N=96")
 
 
+def test_highres_b8_f32_vs_oracle():
+    """configs[4]'s shape at the benchmark's own batch, B=8, 384x1280, N=96, f32 (the `...|B8|...` entries of `bench.py --workload highres`)
+    against the float64 oracle run one sample at a time: the bounds of the B=8 256x512 test, gradients element-wise (grad_parity)."""
+    shape = (8,) + HIGHRES
+    _check_vs_oracle(_stage1(torch.float32, shape), shape, "B=8 384x1280 N=96")
+
+
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 def test_highres_b8_16bit_vs_f32_hip(dt, tmp_path_factory):
     """configs[4] at the benchmark's own batch (the `...|B8|...` autotune entries of `bench.py --workload highres`, the wave-neighbour
     16-bit head backward): f16 (its dtype) and bf16 against the deterministic f32 HIP step of the same inputs (the f32 path is held to the
     oracle at B=1 above), per parameter tensor (NORM_TOL / COS_MIN)."""
     shape = (8,) + HIGHRES
-    _compare_16bit(_f32_det(shape, tmp_path_factory), _stage1(dt, shape), dt, "highres B=8")
+    got = _stage1(dt, shape)
+    _compare_16bit(_f32_det(shape, tmp_path_factory), got, dt, "highres B=8")
+    _compare_16bit_vs_oracle(_oracle64(shape, chunk=1), got, dt, "highres B=8")
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
@@ -158,7 +220,9 @@ def test_stage1_b8_16bit_vs_f32_hip(dt, tmp_path_factory):
     """The benchmark's own dtype (bf16) and f16 at the benchmark's own batch -- the LDS-DMA / weight-stationary / row-streaming 16-bit kernels
     `bench.py` runs -- against the deterministic f32 HIP step of the same inputs, per parameter tensor: gradient norm within 3 % (bf16) /
     0.5 % (f16) and cosine >= 0.999 for EVERY tensor (NORM_TOL / COS_MIN)."""
-    _compare_16bit(_f32_det((B, H, W, N), tmp_path_factory), _stage1(dt), dt, "B=8 256x512")
+    got = _stage1(dt)
+    _compare_16bit(_f32_det((B, H, W, N), tmp_path_factory), got, dt, "B=8 256x512")
+    _compare_16bit_vs_oracle(_oracle64((B, H, W, N)), got, dt, "B=8 256x512")
 
 
 def _stage2(dtype):
@@ -169,11 +233,26 @@ def _stage2(dtype):
     out = train.stage2_step(m, fix, train.FlatAdam(m, lr=5e-5), left.to(DEV), right.to(DEV), mx.to(DEV))
     inv = 1.0 / float(out["scaler"].state[0]) if out.get("scaler") is not None else 1.0  # f16: the raw gradients carry the loss scale
     res = {k: float(out[k]) for k in ("loss", "rec", "sm", "mirror")}
-    res.update(ldisp=out["ldisp"].detach().clone().cpu(), rdisp=out["rdisp"].detach().clone().cpu(), flat_grad=m.flat_gradients().clone() * inv,
+    res.update(ldisp=out["ldisp"].detach().clone().cpu(), rdisp=out["rdisp"].detach().clone().cpu(),
+               O_L=out["O_L"].detach().clone().cpu(), O_R=out["O_R"].detach().clone().cpu(), flat_grad=m.flat_gradients().clone() * inv,
                grads={k: p.grad.detach().float().cpu() * inv for k, p in m.named_parameters() if p.grad is not None})
     del m, fix
     LF.set_compute_dtype(torch.float32)
     return res
+
+
+def test_stage2_b8_f32_vs_oracle():
+    """Stage-2 (BASELINE configs[3]) f32 at the benchmark's batch, B=8, 256x512, N=49 -- the `...|B8|...` cache entries of the 2B-batch plans --
+    against the float64 oracle (run in chunks of two samples): loss scalars and both disparities 1e-4, occlusion masks 2e-4 (as at B=2), every
+    gradient element-wise (grad_parity)."""
+    got, ref = _stage2(torch.float32), _oracle64((B, H, W, N), stage2=True)
+    for k in ("loss", "rec", "sm", "mirror"):
+        assert abs(got[k] - ref[k]) / abs(ref[k]) < TOL, (k, got[k], ref[k])
+    for k in ("O_L", "O_R"):
+        assert rel(got[k], ref[k]) < 2e-4, (k, rel(got[k], ref[k]))
+    for k in ("ldisp", "rdisp"):
+        assert rel(got[k], ref[k]) < TOL, (k, rel(got[k], ref[k]))
+    grad_parity(got["grads"], ref["grads"], norm_tol=2e-3, what="Stage-2 B=8 256x512 f32")
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
@@ -187,6 +266,7 @@ def test_stage2_b8_16bit_vs_f32_hip(dt, tmp_path_factory):
     dev = {k: abs(got[k] - ref[k]) / abs(ref[k]) for k in ("loss", "rec", "sm", "mirror")}
     print(f"Stage-2 B=8 {dt} vs deterministic f32 HIP: {dev}, rdisp {rel(got['rdisp'], ref['rdisp']):.2e}")
     _compare_16bit(ref, got, dt, "Stage-2 B=8", loss_tol=3e-2, disp_tol=1.5e-1 if dt == torch.bfloat16 else 3e-2)
+    _compare_16bit_vs_oracle(_oracle64((B, H, W, N), stage2=True), got, dt, "Stage-2 B=8")
     tol = 3e-2 if dt == torch.bfloat16 else 1e-2
     assert dev["rec"] < tol and dev["sm"] < tol and dev["mirror"] < tol, dev
     assert rel(got["rdisp"], ref["rdisp"]) < (1.5e-1 if dt == torch.bfloat16 else 3e-2)

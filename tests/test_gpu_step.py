@@ -14,6 +14,8 @@ from fal_net_amd import synthetic, train  # noqa: E402
 from fal_net_amd.models import FAL_netB  # noqa: E402
 from oracle import falnet_oracle as O  # noqa: E402
 
+from _grad_parity import grad_parity  # noqa: E402
+
 DEV = "cuda"
 TOL = 1e-4  # north_star gate (f32 path): loss scalars and disparity maps within 1e-4 relative
 
@@ -37,6 +39,13 @@ def check_after_adam(after, golden_after, golden_gsamp, gnorm, numel, key, tol=2
     stable = np.abs(golden_gsamp) > 1e-2 * gnorm / np.sqrt(numel)
     assert d[stable].max(initial=0.0) < tol, key
     assert d.max(initial=0.0) < 2 * lr + tol, key
+
+
+def oracle64(sd, left, right, mn, mx, vsd=None):
+    """Float64 leaf parameters, teacher weights, VGG weights and images for an oracle run without f32 summation noise."""
+    sd = {k: v.double() for k, v in sd.items()}
+    vsd = {k: v.double() for k, v in (vsd or synthetic.seeded_vgg19_state_dict()).items()}
+    return O.leaf_params(sd), sd, vsd, left.double(), right.double(), mn.double(), mx.double()
 
 
 def build(n_levels, dtype=torch.float32):
@@ -84,6 +93,11 @@ def test_stage1_config_shape_vs_golden(golden_dir):
         if ("gnorm:" + k) in g.files:
             gn = float(g["gnorm:" + k])
             assert abs(float(p.grad.norm()) - gn) / gn < 2e-3, k
+    # the golden stores gradient norms only: every gradient element-wise against the float64 oracle on the same inputs
+    p64, _, vsd64, *x64 = oracle64(synthetic.seeded_falnetb_state_dict(49), left, right, mn, mx)
+    O.stage1_losses(p64, vsd64, *x64)["loss"].backward()
+    grad_parity({k: p.grad for k, p in m.named_parameters() if p.grad is not None}, {k: p.grad for k, p in p64.items() if p.grad is not None},
+                norm_tol=2e-3, what="Stage-1 B=1 256x512 (g4 inputs)")
     # abs_rel of depth (myUtils.py:225 style) between HIP and reference disparities
     d_ref, d_hip = 721.5377 * 0.54 / g["disp"], 721.5377 * 0.54 / out["ldisp"].detach()[:, :, ::8, ::8].cpu().numpy()
     assert float(np.mean(np.abs(d_ref - d_hip) / d_ref)) < 1e-5
@@ -144,6 +158,11 @@ def test_stage2_step_vs_golden(golden_dir):
         if ("gnorm:" + k) in g.files:
             gn = float(g["gnorm:" + k])
             assert abs(float(p.grad.norm()) - gn) / gn < 1e-3, k
+    # the golden stores gradient norms only: every gradient element-wise against the float64 oracle on the same inputs
+    p64, sd64, vsd64, *x64 = oracle64(synthetic.seeded_falnetb_state_dict(7), left, right, mn, mx)
+    O.stage2_losses(p64, sd64, vsd64, *x64)["loss"].backward()
+    grad_parity({k: p.grad for k, p in m.named_parameters() if p.grad is not None}, {k: p.grad for k, p in p64.items() if p.grad is not None},
+                norm_tol=1e-3, what="Stage-2 B=2 64x128 (g3 inputs)")
 
 
 def test_stage1_slow_step_vs_golden(golden_dir):
@@ -241,6 +260,11 @@ def test_stage2_step_falnetA_vs_oracle():
     for k, p in m.named_parameters():
         gn = float(params[k].grad.norm())
         assert abs(float(p.grad.norm()) - gn) / gn < 1e-3, k
+    # element-wise against the float64 oracle
+    p64, sd64, vsd64, *x64 = oracle64(sd, left, right, mn, mx)
+    O.stage2_losses(p64, sd64, vsd64, *x64)["loss"].backward()
+    grad_parity({k: p.grad for k, p in m.named_parameters() if p.grad is not None}, {k: p.grad for k, p in p64.items() if p.grad is not None},
+                norm_tol=1e-3, what="Stage-2 FAL_netA 64x128")
 
 
 def test_16bit_steps_run_and_track_f32():
@@ -453,14 +477,15 @@ def test_deterministic_f32_trajectories_are_identical():
 
 def test_stage2_step_256x512_vs_oracle():
     """Stage-2 step at the benchmark resolution (BASELINE configs[3]: 256 x 512, N = 49; B = 2 here, f32) against the CPU oracle:
-    loss scalars, both occlusion masks and every parameter's gradient norm (the 64 x 128 case is pinned by golden G3)."""
+    loss scalars, both occlusion masks and every parameter's gradient -- norm and element-wise (grad_parity) against the float64 oracle
+    (the 64 x 128 case is pinned by golden G3)."""
     LF.set_compute_dtype(torch.float32)
     sd = synthetic.seeded_falnetb_state_dict(49)
     left, right, mn, mx = synthetic.synthetic_pair(2, 256, 512, seed=41, distinct=True)
     m, fix = build(49).train(), build(49).eval()
     out = train.stage2_step(m, fix, train.FlatAdam(m, lr=5e-5), left.to(DEV), right.to(DEV), mx.to(DEV))
-    params = O.leaf_params(sd)
-    ref = O.stage2_losses(params, sd, synthetic.seeded_vgg19_state_dict(), left, right, mn, mx)
+    params, sd64, vsd64, *x64 = oracle64(sd, left, right, mn, mx)  # float64: the f32 oracle's own sums over 131k pixels needed 1e-3 here
+    ref = O.stage2_losses(params, sd64, vsd64, *x64)
     for k in ("loss", "rec", "sm", "mirror"):
         assert abs(float(out[k]) - float(ref[k])) / abs(float(ref[k])) < TOL, (k, float(out[k]), float(ref[k]))
     for k in ("O_L", "O_R"):
@@ -470,7 +495,9 @@ def test_stage2_step_256x512_vs_oracle():
         if params[k].grad is None:
             continue
         gn = float(params[k].grad.norm())
-        assert abs(float(p.grad.norm()) - gn) / gn < 2e-3, (k, float(p.grad.norm()), gn)  # (the reference itself needs 1e-3 here: f32 sums over 131k pixels)
+        assert abs(float(p.grad.norm()) - gn) / gn < 2e-3, (k, float(p.grad.norm()), gn)
+    grad_parity({k: p.grad for k, p in m.named_parameters() if params[k].grad is not None},
+                {k: p.grad for k, p in params.items() if p.grad is not None}, norm_tol=2e-3, what="Stage-2 B=2 256x512")
 
 
 def test_vgg_plans_are_released_and_shared_feature_gradients_sum():
