@@ -79,8 +79,6 @@ def main(step='stage1_step'):
     if world > 1:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl', device_id=dev)
-    if args.weight_decay or args.bias_decay:
-        raise SystemExit('weight decay is 0 in the reference defaults; the fused flat Adam implements wd=0 only')
     dtype = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[args.dtype]
     LF.set_compute_dtype(dtype)
 
@@ -112,7 +110,12 @@ def main(step='stage1_step'):
     if rank == 0:
         print("=> Number of parameters m-model '{}'".format(utils.get_n_params(m_model)))
     train.sync_parameters(m_model)  # N > 1: rank 0's weights to every rank, once (then one gradient all-reduce per step)
-    opt = train.FlatAdam(m_model, lr=args.lr, betas=(args.momentum, args.beta))
+    # two Adam param groups in the reference (Train_Stage1_K.py:177-180): biases decay by --bias-decay, weights by --weight-decay
+    opt = train.FlatAdam(m_model, lr=args.lr, betas=(args.momentum, args.beta), weight_decay=args.weight_decay, bias_decay=args.bias_decay)
+    if isinstance(network_data, dict) and network_data.get('optimizer', {}).get('step') == step:
+        # resumed run of the SAME stage: continue the moments and the bias corrections (the decays given on THIS command line hold, like the
+        # learning rate).  A Stage-2 run started from a Stage-1 checkpoint begins with a fresh optimiser, as in the reference.
+        opt.load_state_dict(dict(network_data['optimizer'], weight_decay=args.weight_decay, bias_decay=args.bias_decay))
 
     def lr_at(epoch):  # MultiStepLR(milestones, gamma=0.5), fast-forwarded like Train_Stage1_K.py:181-184
         return args.lr * (0.5 ** sum(1 for m in args.milestones if epoch >= m))
@@ -223,6 +226,7 @@ def main(step='stage1_step'):
             sc = train.loss_scaler(m_model)
             if sc is not None:
                 ckpt['loss_scaler'] = sc.state_dict()  # (an extra key: the reference's loader reads only the four above)
+            ckpt['optimizer'] = dict(opt.state_dict(), step=step)  # (another extra key: step count, moments, decays, parameter layout, which stage)
             utils.save_checkpoint(ckpt, is_best, save_path)
     if world > 1:
         dist.destroy_process_group()

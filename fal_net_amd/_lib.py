@@ -115,6 +115,8 @@ SIGNATURES = {
     "falnet_adam_pack_batched": [_P, _I, _I, _I, _L, _L, _L, _P, _F, _F, _F, _F, _P, _P],
     "falnet_adam_ranges": [_P, _L, _L, _L, _P, _I, _P, _F, _F, _F, _F, _P, _P],
     "falnet_adam_tick": [_P, _P, _P],
+    "falnet_adam_pack_batched_wd": [_P, _I, _I, _I, _L, _L, _L, _P, _F, _F, _F, _F, _D, _P, _P],
+    "falnet_adam_ranges_wd": [_P, _L, _L, _L, _P, _P, _I, _P, _F, _F, _F, _F, _P, _P],
     "falnet_pack_up2_batched": [_P, _I, _I, _I, _P],
     "falnet_wgrad_reduce_batched": [_P, _I, _I, _I, _P],
     "falnet_wgrad_reduce_blocks": [_I, _I, _I],
@@ -150,6 +152,7 @@ SIGNATURES = {
     "falnet_adam_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P],
     "falnet_adam_step_dev": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P],
     "falnet_adam_step_guarded": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _P],
+    "falnet_adam_step_wd": [_P, _P, _P, _P, _L, _P, _P, _I, _P, _F, _F, _F, _F, _P, _P],
     "falnet_grad_guard": [_P, _L, _P, _P],
     "falnet_loss_scale_update": [_P, _F, _F, _I, _F, _F, _P],
     "falnet_loss_seeds": [_P, _P, _P, _I, _P],

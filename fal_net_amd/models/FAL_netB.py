@@ -187,6 +187,18 @@ class FAL_net(nn.Module):
         self._plans = {}
         self._build_packed()
 
+    def decay_segments(self):
+        """[(first element, padded element count, is a bias)] of every trainable parameter, in flat-buffer order: the slices tile the buffer
+        (each one carries its own 16-B padding).  The kind decides the decay (reference Train_Stage1_K.py:177-178: `bias_parameters()` get
+        bias_decay, `weight_parameters()` weight_decay); amask_conv is outside the buffer, neither updated nor decayed."""
+        named, total = self._trainable_named(), self._flat.numel()
+        out = []
+        for i, ((n, p), off) in enumerate(zip(named, self._offsets)):
+            if ("bias" in n) == ("weight" in n):
+                raise RuntimeError(f"parameter {n} is neither a bias nor a weight: no decay group for it")
+            out.append((off, (self._offsets[i + 1] if i + 1 < len(named) else total) - off, "bias" in n))
+        return out
+
     def _packed_is_fresh(self):
         """True when the packed compute-dtype weight copies already match the f32 masters: FlatAdam re-packs right behind its
         update (`repack_after_optimizer`), and nothing has written the flat buffer in place since (shared version counter of
@@ -212,10 +224,11 @@ class FAL_net(nn.Module):
             call()
         self._packed_version = self._weights_version()
 
-    def adam_and_repack(self, grad, m, v, state, b1, b2, eps, grad_scale, scaler_state):
+    def adam_and_repack(self, grad, m, v, state, b1, b2, eps, grad_scale, scaler_state, weight_decay=0.0, bias_decay=0.0):
         """torch.optim.Adam's update of the whole flat buffer AND the re-pack of the compute-dtype weight copies: one pass over the masters
         of the packed layers (falnet_adam_pack_batched), a range list for the rest, then the derived weights.  Returns False when no plan
-        exists yet (the caller runs the stand-alone update)."""
+        exists yet (the caller runs the stand-alone update).  With a non-zero decay the same sequence runs through the decayed entry points
+        (falnet_adam_ranges_wd over the ranges cut at parameter boundaries, falnet_adam_pack_batched_wd); both 0: exactly the launches above."""
         plan = next(iter(self._plans.values()), None)
         ap = getattr(plan, "adam_pack", None)
         if ap is None or torch.cuda.is_current_stream_capturing():
@@ -223,13 +236,19 @@ class FAL_net(nn.Module):
         flat = self._flat
         g_off, m_off, v_off = ((t.data_ptr() - flat.data_ptr()) // 4 for t in (grad, m, v))
         lib, st = L.lib(), L.stream_ptr()
-        if ap["rest"] is not None:
+        if weight_decay or bias_decay:
+            wd = plan.adam_ranges_wd()
+            if wd is not None:
+                ranges, table, n_ranges = wd
+                L.check(lib.falnet_adam_ranges_wd(L.ptr(flat), g_off, m_off, v_off, L.ptr(ranges), L.ptr(table.get(weight_decay, bias_decay)), n_ranges,
+                                                  L.ptr(state), b1, b2, eps, float(grad_scale), L.ptr(scaler_state), st), "adam_ranges_wd")
+        elif ap["rest"] is not None:
             L.check(lib.falnet_adam_ranges(L.ptr(flat), g_off, m_off, v_off, L.ptr(ap["rest"]), ap["n_rest"], L.ptr(state), b1, b2, eps, float(grad_scale),
                                            L.ptr(scaler_state), st), "adam_ranges")
         for call in ap["before"]:
             call()
         if ap["owned"] is not None:
-            ap["owned"](g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler_state)
+            ap["owned"](g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler_state, weight_decay)
         L.check(lib.falnet_adam_tick(L.ptr(state), L.ptr(scaler_state), st), "adam_tick")
         for call in ap["after"]:
             call()

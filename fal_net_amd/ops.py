@@ -285,7 +285,8 @@ def pack_all_call(pcs, dtype, device):
 def adam_pack_call(pcs, dtype, device, derived=()):
     """ONE launch = the Adam update of every layer in `pcs` (f32 masters inside the model's flat buffer) + its re-pack into wf / wd
     (falnet_adam_pack_batched); the layers in `derived` (masters outside the flat buffer, rebuilt from updated factors before this launch)
-    are only packed.  Returns launch(g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler_ptr_or_None)."""
+    are only packed.  Returns launch(g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler_ptr_or_None, weight_decay=0.0); a non-zero
+    weight_decay (read at every call, never cached) selects falnet_adam_pack_batched_wd: every layer packed here is a weight."""
     lib = L.lib()
     n_own = len(pcs)
     pcs = list(pcs) + list(derived)
@@ -302,10 +303,32 @@ def adam_pack_call(pcs, dtype, device, derived=()):
     dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device)
     n, total, code = len(pcs), blk, L.dtype_code(dtype)
 
-    def launch(g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler, _keep=(dev, pcs)):
+    def launch(g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler, weight_decay=0.0, _keep=(dev, pcs)):
+        if weight_decay:
+            L.check(lib.falnet_adam_pack_batched_wd(L.ptr(dev), n, total, code, g_off, m_off, v_off, L.ptr(state), b1, b2, eps, float(grad_scale),
+                                                    float(weight_decay), L.ptr(scaler), L.stream_ptr()), "adam_pack_batched_wd")
+            return
         L.check(lib.falnet_adam_pack_batched(L.ptr(dev), n, total, code, g_off, m_off, v_off, L.ptr(state), b1, b2, eps, float(grad_scale),
                                              L.ptr(scaler), L.stream_ptr()), "adam_pack_batched")
     return launch
+
+
+class DecayTable:
+    """f64 device array (the kernels form g + decay * p in double) of one decay per entry -- a range of falnet_adam_ranges_wd, a segment of
+    falnet_adam_step_wd: bias_decay where `is_bias[i]`, weight_decay elsewhere.  get() rewrites it (one small copy on the current stream) only when a value differs from the last
+    call, so a decay changed between two steps holds from the next step on and an unchanged one costs nothing."""
+
+    def __init__(self, is_bias, device):
+        self.is_bias = [bool(b) for b in is_bias]
+        self.dev = torch.zeros(len(self.is_bias), dtype=torch.float64, device=device)
+        self.key = (0.0, 0.0)
+
+    def get(self, weight_decay, bias_decay):
+        key = (float(weight_decay), float(bias_decay))
+        if key != self.key:
+            self.dev.copy_(torch.tensor([key[1] if b else key[0] for b in self.is_bias], dtype=torch.float64))
+            self.key = key
+        return self.dev
 
 
 def pack_up2_call(pcs, dtype, device):

@@ -141,6 +141,10 @@ class StepStreams:
             return
         if (main.cuda_stream, bool(hooked)) in self.tested:
             return
+        if torch.cuda.is_current_stream_capturing():
+            # train.GraphedStage1Step: the capture stream is a caller's stream the test has not seen, and the test synchronises the device and
+            # times spins -- neither can be captured, and a graph's branches are placed by the executor, not by these stream handles
+            return
         # the collective part runs once per device (normally at train.enable_overlapped_allreduce); a later visit from another caller's stream, or
         # after a local replacement, repeats only the LOCAL pair part -- no rank ever issues a probe collective its peers do not
         again = bool(hooked) and self.hooked_tested
@@ -521,6 +525,26 @@ class FalnetPlan:
                     c()
         pend.clear()
 
+    def adam_ranges_wd(self):
+        """(ranges, ops.DecayTable, count) of the DECAYED range update (falnet_adam_ranges_wd), or None when the packed layers cover the flat
+        buffer.  A range needs ONE decay, and the gaps of adam_pack['rest'] run across neighbours of different kinds (a bias and the unpacked
+        1x1 conv0 weight, the factors of the composed logits weights): the same gaps, cut at the parameter boundaries.  Built on first use --
+        a run with both decays 0 never asks for it and keeps the uncut list, the same launch as ever."""
+        ap = self.adam_pack
+        if ap["rest_wd"] is None and ap["rest_host"]:
+            rest, ranges, is_bias = ap["rest_host"], [], []
+            segs = self.model.decay_segments()
+            for r in range(0, len(rest), 2):
+                a, end = rest[r], rest[r] + rest[r + 1]
+                for off, cnt, bias in segs:
+                    lo, hi = max(a, off), min(end, off + cnt)
+                    if lo < hi:
+                        ranges += [lo, hi - lo]
+                        is_bias.append(bias)
+            assert sum(ranges[1::2]) == sum(rest[1::2])  # (the slices tile the flat buffer: nothing of a gap is lost by the cut)
+            ap["rest_wd"] = (torch.tensor(ranges, dtype=torch.int64, device=self.device), ops.DecayTable(is_bias, self.device), len(is_bias))
+        return ap["rest_wd"]
+
     # ---- plan construction ----
     def _build(self):
         m, B, H, W, N, dt, dev = self.model, self.B, self.H, self.W, self.N, self.dtype, self.device
@@ -566,6 +590,7 @@ class FalnetPlan:
             rest += [pos, flat.numel() - pos]
         self.adam_pack = dict(
             rest=torch.tensor(rest, dtype=torch.int64, device=dev) if rest else None, n_rest=len(rest) // 2,
+            rest_host=rest, rest_wd=None,  # (the decayed form of the range list: built by adam_ranges_wd() on its first use)
             before=[compose_call] if compose else [],  # (needs the factors the range update has just written)
             owned=ops.adam_pack_call(owned, dt, dev, derived) if owned else None,
             after=[up2] if up2 is not None else [])

@@ -17,65 +17,155 @@ _FORCE_DIST = _os.environ.get("FALNET_FORCE_DIST") == "1"  # exercise the collec
 
 
 class FlatAdam:
-    """Adam(betas, eps, weight_decay=0) over `model.flat_parameters()` (torch.optim.Adam semantics).
+    """Adam(betas, eps) over `model.flat_parameters()` with torch.optim.Adam's semantics, including its L2 weight decay (not AdamW).
 
-    Both of the reference's param groups (biases / weights, Train_Stage1_K.py:177-178) use weight_decay 0,
-    so one flat update is identical to the two-group optimiser.  amask_conv never receives gradients and
-    is skipped exactly like torch skips `grad is None` parameters."""
+    The reference builds two param groups (Train_Stage1_K.py:177-180): biases with `weight_decay=args.bias_decay`, weights with
+    `weight_decay=args.weight_decay`.  Here both live in ONE flat buffer and one fused update: a parameter whose name contains `bias` is
+    decayed by `bias_decay`, one whose name contains `weight` by `weight_decay` (gr = g * grad_scale / loss scale + decay * p, then the
+    moments and the step).  With both decays 0 (the default, and the reference's default) the launches are exactly those of the
+    undecayed optimiser.  Both values are read at every step(): changing `opt.weight_decay` / `opt.bias_decay` between steps holds from the
+    next step on (a captured step, GraphedStage1Step, reads device tables that only an eager step() rewrites: after changing a decay run one
+    eager step, then replay).  `param_groups[0]['lr']` is the single learning rate.  amask_conv never receives gradients and is neither updated nor
+    decayed, exactly like torch skips `grad is None` parameters.  state_dict() / load_state_dict(): step count, both moments, both decays
+    and the parameter layout, so that a resumed run continues its moments and bias corrections instead of restarting them."""
 
-    def __init__(self, model, lr=1e-4, betas=(0.5, 0.999), eps=1e-8):
+    def __init__(self, model, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, bias_decay=0.0):
+        if weight_decay < 0 or bias_decay < 0:
+            raise ValueError(f"FlatAdam: negative decay (weight_decay={weight_decay}, bias_decay={bias_decay})")
         self.model, self.betas, self.eps = model, betas, eps
+        self.weight_decay, self.bias_decay = float(weight_decay), float(bias_decay)
         self.param_groups = [{"lr": lr}]
         self.t = 0
         self.m = self.v = None
+        self._segments = None
 
     def zero_grad(self, set_to_none=True):
         for p in self.model.parameters():
             p.grad = None
 
+    # ---- checkpointing ----
+    def _layout(self):
+        """name -> (offset, numel) of every trainable parameter in the flat buffer (None before the buffer exists)."""
+        m = self.model
+        if m.flat_parameters() is None:
+            return None
+        return {n: (int(off), int(p.numel())) for (n, p), off in zip(m._trainable_named(), m._offsets)}
+
+    def state_dict(self):
+        """{'t', 'm', 'v' (CPU f32 copies of the moments, None before the first step), 'weight_decay', 'bias_decay', 'layout'}.  `t` is the
+        DEVICE step count once a step has run (a step skipped by the f16 guard advances neither it nor the bias corrections); reading it
+        synchronises, like every checkpoint does."""
+        t = self.t if self.m is None else int(round(float(self.state[1])))
+        return {"t": t, "m": None if self.m is None else self.m.detach().cpu().clone(), "v": None if self.v is None else self.v.detach().cpu().clone(),
+                "weight_decay": self.weight_decay, "bias_decay": self.bias_decay, "layout": self._layout()}
+
+    def load_state_dict(self, sd):
+        """Restore what state_dict() saved.  The moments are addressed by flat-buffer offset, so a model laid out differently (another
+        no_levels, another variant) is refused: ValueError, nothing changed.  Call it with the model on the device it will train on (the moments
+        are placed beside the model's flat buffer; like the first step's, they do not follow a later `.to()`)."""
+        if (sd["m"] is None) != (sd["v"] is None):
+            raise ValueError("FlatAdam.load_state_dict: one moment without the other")
+        if sd["layout"] is not None:
+            flat = self.model.ensure_flat()  # (the layout is fixed by the module tree; the first forward would build the same buffer)
+            theirs, mine = {n: tuple(v) for n, v in sd["layout"].items()}, self._layout()
+            if theirs != mine:
+                bad = sorted(n for n in set(mine) | set(theirs) if mine.get(n) != theirs.get(n))
+                raise ValueError(f"FlatAdam.load_state_dict: the state was saved for another parameter layout ({len(bad)} entries differ, "
+                                 f"first {bad[0]}: saved {theirs.get(bad[0])}, this model {mine.get(bad[0])})")
+            if sd["m"] is not None and (sd["m"].numel() != flat.numel() or sd["v"].numel() != flat.numel()):
+                raise ValueError(f"FlatAdam.load_state_dict: moments of {sd['m'].numel()} / {sd['v'].numel()} elements for a flat buffer of {flat.numel()}")
+        elif sd["m"] is not None:
+            raise ValueError("FlatAdam.load_state_dict: moments without the layout they were saved for")
+        self.weight_decay, self.bias_decay = float(sd["weight_decay"]), float(sd["bias_decay"])
+        self.t = int(sd["t"])
+        self.m = self.v = None
+        if sd["m"] is not None:
+            self._alloc(flat)
+            self.m.copy_(sd["m"].to(torch.float32).reshape(-1))
+            self.v.copy_(sd["v"].to(torch.float32).reshape(-1))
+
+    def _alloc(self, flat):
+        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
+        # hyper-state {lr, t} lives on the device so that a captured hipGraph advances the step count
+        self.state = torch.tensor([float(self.param_groups[0]["lr"]), float(self.t)], device=flat.device)
+        self._lr_dev = float(self.param_groups[0]["lr"])
+        self._segments = None
+
+    def _decay_segments(self, flat):
+        """Device tables of the stand-alone decayed update (falnet_adam_step_wd): one segment per parameter slice, (ends, decays, count).
+        Building them and rewriting a changed decay are host-to-device copies, so both happen OUTSIDE stream capture only: step() calls this
+        on every decayed step, whichever path the update then takes, so the eager warm-up steps before a capture leave the tables current.
+        Under capture they are used as they are; missing or stale ones are an error, never a copy recorded into the graph."""
+        key = (float(self.weight_decay), float(self.bias_decay))
+        if flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            if self._segments is None or self._segments[1].key != key:
+                raise RuntimeError(f"FlatAdam: stream capture with weight_decay / bias_decay {key} needs one eager step() with these values first "
+                                   "(the decay tables are written by host-to-device copies, which cannot be captured)")
+            ends, table, n = self._segments
+            return ends, table.dev, n
+        if self._segments is None:
+            segs = self.model.decay_segments()
+            ends = torch.tensor([off + cnt for off, cnt, _ in segs], dtype=torch.int64, device=flat.device)
+            self._segments = (ends, ops.DecayTable([b for _, _, b in segs], flat.device), len(segs))
+        ends, table, n = self._segments
+        return ends, table.get(*key), n
+
     def step(self, grad_scale=1.0, scaler=None):
         """`scaler`: the model's LossScaler (f16 path) -- the update then divides the gradients by the device-resident scale, is
-        skipped as a whole when the all-reduced gradient holds an inf / NaN, and the scale backs off / grows (GradScaler semantics)."""
+        skipped as a whole (decay included) when the all-reduced gradient holds an inf / NaN, and the scale backs off / grows (GradScaler semantics)."""
         flat, grad = self.model.flat_parameters(), self.model.flat_gradients()
         if flat is None:
             raise RuntimeError("FlatAdam.step before any forward/backward of the model")
         if self.m is None or self.m.numel() != flat.numel() or self.m.device != flat.device:
-            self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-            # hyper-state {lr, t} lives on the device so that a captured hipGraph advances the step count
-            self.state = torch.tensor([float(self.param_groups[0]["lr"]), float(self.t)], device=flat.device)
-            self._lr_dev = float(self.param_groups[0]["lr"])
+            self._alloc(flat)
         if self._lr_dev != float(self.param_groups[0]["lr"]):
             self._lr_dev = float(self.param_groups[0]["lr"])
             self.state[0] = self._lr_dev
         self.t += 1
         b1, b2 = self.betas
+        wd, bd = float(self.weight_decay), float(self.bias_decay)
+        decayed = bool(wd or bd)
+        segments = self._decay_segments(flat) if decayed else None  # (kept current on every decayed step: see there)
         if _ADAM_PACK and hasattr(self.model, "adam_and_repack"):
             # the update of the packed layers rides in the launch that re-packs them (one pass over the f32 masters instead of two)
             if scaler is not None:
                 L.check(L.lib().falnet_grad_guard(L.ptr(grad), grad.numel(), L.ptr(scaler.state), L.stream_ptr()), "grad_guard")
-            if self.model.adam_and_repack(grad, self.m, self.v, self.state, b1, b2, self.eps, grad_scale, None if scaler is None else scaler.state):
+            if self.model.adam_and_repack(grad, self.m, self.v, self.state, b1, b2, self.eps, grad_scale, None if scaler is None else scaler.state,
+                                          weight_decay=wd, bias_decay=bd):
                 if scaler is not None:
                     scaler.update()
                 return
             if scaler is not None:  # (no plan yet: fall through to the stand-alone update; the guard has run)
-                L.check(L.lib().falnet_adam_step_guarded(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(self.state),
-                                                         b1, b2, self.eps, float(grad_scale), L.ptr(scaler.state), L.stream_ptr()), "adam_step_guarded")
+                self._standalone(flat, grad, b1, b2, grad_scale, scaler, segments)
                 scaler.update()
                 self.model.mark_weights_changed()
                 return
         if scaler is None:
-            L.check(L.lib().falnet_adam_step_dev(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(self.state),
-                                                 b1, b2, self.eps, float(grad_scale), L.stream_ptr()), "adam_step_dev")
+            self._standalone(flat, grad, b1, b2, grad_scale, None, segments)
         else:
-            st = L.stream_ptr()
-            L.check(L.lib().falnet_grad_guard(L.ptr(grad), grad.numel(), L.ptr(scaler.state), st), "grad_guard")
-            L.check(L.lib().falnet_adam_step_guarded(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(self.state),
-                                                     b1, b2, self.eps, float(grad_scale), L.ptr(scaler.state), st), "adam_step_guarded")
+            L.check(L.lib().falnet_grad_guard(L.ptr(grad), grad.numel(), L.ptr(scaler.state), L.stream_ptr()), "grad_guard")
+            self._standalone(flat, grad, b1, b2, grad_scale, scaler, segments)
             scaler.update()
         if L.ab("FALNET_PACK_AFTER_ADAM", "1") == "1":
             self.model.repack_after_optimizer()  # the raw-pointer update is invisible to autograd's version counters
         else:
             self.model.mark_weights_changed()
+
+    def _standalone(self, flat, grad, b1, b2, grad_scale, scaler, segments):
+        """The flat update as a launch of its own (no plan yet, pack fusion off, stream capture), then the step-count tick.
+        `segments`: _decay_segments() of a decayed step, None otherwise."""
+        lib, st = L.lib(), L.stream_ptr()
+        if segments is not None:
+            ends, decays, n_seg = segments
+            L.check(lib.falnet_adam_step_wd(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(ends), L.ptr(decays), n_seg,
+                                            L.ptr(self.state), b1, b2, self.eps, float(grad_scale), L.ptr(None if scaler is None else scaler.state), st),
+                    "adam_step_wd")
+        elif scaler is None:
+            L.check(lib.falnet_adam_step_dev(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(self.state),
+                                             b1, b2, self.eps, float(grad_scale), st), "adam_step_dev")
+        else:
+            L.check(lib.falnet_adam_step_guarded(L.ptr(flat), L.ptr(grad), L.ptr(self.m), L.ptr(self.v), flat.numel(), L.ptr(self.state),
+                                                 b1, b2, self.eps, float(grad_scale), L.ptr(scaler.state), st), "adam_step_guarded")
 
 
 # f16 compute path: activation gradients are stored in IEEE half (normal range >= 6.1e-5) while a mean loss over B*3*H*W

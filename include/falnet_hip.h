@@ -272,6 +272,19 @@ int falnet_adam_ranges(float* p, int64_t g_off, int64_t m_off, int64_t v_off, co
                        float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream);
 /* t += 1 unless the scaler's overflow flag is set (a skipped step does not count) */
 int falnet_adam_tick(float* state, const float* scaler, void* stream);
+/* Weight decay / bias decay (torch.optim.Adam's L2 form, not AdamW: the two param groups of Train_Stage1_K.py:177-180).  With gr the gradient
+ * after grad_scale and the f16 loss-scale division: gr += decay * p, then the moments and the step of the functions above; a raised overflow
+ * flag skips the update AND the decay.  The 16-B padding elements between parameter slices (p = g = 0) stay exactly 0.  The decays are
+ * DOUBLES and gr is rounded to f32 once: where g and decay * p cancel, an f32 sum would put the young-moment step outside an f64 reference's reach.
+ * falnet_adam_pack_batched_wd: falnet_adam_pack_batched with ONE decay for the launch -- every packed layer is a convolution weight;
+ *   no_update entries are only packed.
+ * falnet_adam_ranges_wd: falnet_adam_ranges with decays_dev[r] (f64) the decay of range r; a range must not span two parameters of
+ *   different decay.  Neither advances t (falnet_adam_tick). */
+int falnet_adam_pack_batched_wd(const falnet_pack_t* descs_dev, int n, int total_blocks, int dtype, int64_t g_off, int64_t m_off, int64_t v_off,
+                                const float* state, float b1, float b2, float eps, float grad_scale, double weight_decay, const float* scaler,
+                                void* stream);
+int falnet_adam_ranges_wd(float* p, int64_t g_off, int64_t m_off, int64_t v_off, const int64_t* ranges_dev, const double* decays_dev, int n_ranges,
+                          const float* state, float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream);
 /* Sub-pixel weights of the `deconv` layers (falnet_conv_t::weight_up2; FAL_netB.py:52-58), all layers in one launch: entry i sums the f32 OIHW
  * 3x3 master weights w into wu [cout_pad][16][cin_pad] (`dtype`; pair index 4 (2 py + px) + 2 a + b, rows / columns: py = 0 -> (W[0], W[1] + W[2]),
  * py = 1 -> (W[0] + W[1], W[2])); an entry uses (cout_pad / 32) * (cin_pad / 32) blocks from block_begin. */
@@ -428,6 +441,11 @@ int falnet_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n
 int falnet_grad_guard(const float* g, int64_t n, float* scaler, void* stream);
 int falnet_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float* state, float b1, float b2,
                              float eps, float grad_scale, const float* scaler, void* stream);
+/* falnet_adam_step_dev / _guarded (scaler NULL / not NULL) with a decay per SEGMENT of the flat buffer: seg_end_dev[s] (int64) = exclusive end
+ * element of segment s, ascending, multiples of 4 (parameter slices are 16-B aligned), the last one >= n; seg_decay_dev[s] (f64) its decay;
+ * 1 <= n_seg <= 1024.  Same float4 streaming pass; advances t like they do. */
+int falnet_adam_step_wd(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end_dev, const double* seg_decay_dev, int n_seg,
+                        float* state, float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream);
 int falnet_loss_scale_update(float* scaler, float growth, float backoff, int interval, float min_scale, float max_scale, void* stream);
 int falnet_loss_seeds(const float* scaler, const float* coef, float* seeds, int n, void* stream);
 
