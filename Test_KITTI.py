@@ -9,8 +9,9 @@ Two modes:
     chain is host-side numpy exactly as in the reference (fal_net_amd.myUtils).
   * `--synthetic`: seeded image of `--height x --width` (native KITTI 375x1242 by default), timing only -- no dataset on the box.
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
-(:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is I/O cosmetics and not provided: `-save*` parse
-and are refused when true.  `--dtype f16` is the recommended 16-bit
+(:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
+fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
+reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
 import argparse
 import json
@@ -77,6 +78,22 @@ parser.add_argument('--iters', type=int, default=10)
 parser.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
 
 
+def _dump_kinds(v):
+    kinds = [k for k in v.split(',') if k]
+    bad = [k for k in kinds if k not in ('disp', 'input', 'pan', 'pc', 'feats')]
+    if bad:
+        raise argparse.ArgumentTypeError('unknown dump kind(s) {}: choose from disp,input,pan,pc,feats'.format(','.join(bad)))
+    return kinds
+
+
+parser.add_argument('--dump', type=_dump_kinds, default=[], metavar='KINDS',
+                    help='comma-separated subset of disp,input,pan,pc,feats: per-frame outputs of the reference\'s test script (:211-253) written under the '
+                         'save path in its folders (l_disp, "Input im", Pan, Point_cloud, feats), finished on the GPU; --synthetic dumps its one frame')
+parser.add_argument('--ply-format', default='binary', choices=['binary', 'ascii'], help='point clouds: binary_little_endian records, or the reference\'s ASCII file')
+parser.add_argument('--device-percentile', action='store_true', help="ms_pp's 95th percentile from the exact device-side percentile kernel instead of the "
+                    'copy to the host and np.percentile')
+
+
 def checkpoint_path(a):
     """Test_KITTI.py:119-120: os.path.join(args.dataset, args.time_stamp, args.model + args.details); --checkpoint overrides."""
     return a.checkpoint or os.path.join(a.dataset, a.time_stamp, a.model + a.details)
@@ -114,6 +131,12 @@ def main():
     m_name = data.get('m_model', args.model) if isinstance(data, dict) else args.model  # :122
     pan_model = models.__dict__[m_name](data, no_levels=args.no_levels, compute_dtype=dtype).to(dev).eval()
     n_params = utils.get_n_params(pan_model)
+    save_path = args.save_path or (os.path.join('Test_Results', args.tdataName, args.model, args.time_stamp)  # :81-85
+                                   + ('fpp' if args.f_post_process else '') + ('mspp' if args.ms_post_process else ''))
+    writer = None
+    if args.dump:
+        from fal_net_amd import dumps
+        writer = dumps.FrameWriter(save_path, args.dump, ply_format=args.ply_format)
 
     if dataset_mode:
         from fal_net_amd import datasets as DS
@@ -124,15 +147,13 @@ def main():
         if not triples:
             raise SystemExit('no test frame with ground truth found under {}'.format(root))
         loader = DS.make_loader(DS.StereoValDataset(root, triples), 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
-        save_path = args.save_path or (os.path.join('Test_Results', args.tdataName, args.model, args.time_stamp)  # :81-85
-                                       + ('fpp' if args.f_post_process else '') + ('mspp' if args.ms_post_process else ''))
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items()))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
-                                 with_metrics=args.evaluate)
+                                 with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))
@@ -157,9 +178,11 @@ def main():
             if args.f_post_process:
                 disp = inference.flip_post_process(left, pan_model, disp, min_disp, max_disp)
             elif args.ms_post_process:
-                disp = inference.ms_pp(left, pan_model, disp, min_disp, max_disp)
+                disp = inference.ms_pp(left, pan_model, disp, min_disp, max_disp, args.device_percentile)
             torch.cuda.synchronize()
             times.append(time.time() - t0)
+        if writer is not None:  # the one seeded frame, after the timed loop
+            inference.dump_frame(writer, 0, pan_model, left, disp, min_disp, max_disp)
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))
 

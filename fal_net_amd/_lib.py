@@ -172,8 +172,15 @@ SIGNATURES = {
     "falnet_copy_bytes": [_P, _P, _L, _P],
     "falnet_spin": [_I, _P],
     "falnet_mfma_probe": [_P, _P, _I, _I, _P],
+    "falnet_percentile_workspace_bytes": [_I],
+    "falnet_percentile_f32": [_P, _L, _I, _D, _P, _P, _P],
+    "falnet_disp_to_plasma_u8": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "falnet_image_to_u8": [_P, _F, _F, _F, _P, _I, _I, _I, _P],
+    "falnet_feature_to_u8": [_P, _P, _L, _P],
+    "falnet_local_norm": [_P, _F, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    "falnet_point_cloud": [_P, _F, _F, _F, _F, _P, _D, _D, _P, _P, _I, _I, _I, _P],
 }
-_RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64}
+_RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

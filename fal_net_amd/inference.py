@@ -1,6 +1,7 @@
 """Inference post-processing of Test_KITTI.py (ms_pp :287-300, flip post-process :200-203) around the HIP model.
 The resampling of the 1- and 3-channel maps (bilinear x2/3, nearest back) goes through falnet_resize_planar; only the
-host-side 95th percentile stays in numpy exactly as in the reference; the two network forwards are the HIP plan."""
+host-side 95th percentile stays in numpy exactly as in the reference (opt-in: the exact device-side percentile of dumps.py); the two
+network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter)."""
 import math
 
 import numpy as np
@@ -20,8 +21,10 @@ def resize_planar(x, size, bilinear, scale=1.0):
     return out
 
 
-def ms_pp(input_view, pan_model, disp, min_disp, max_pix):
-    """Test_KITTI.py:287-300: second forward on the flipped, x2/3-downscaled view; blend by normalised disparity."""
+def ms_pp(input_view, pan_model, disp, min_disp, max_pix, device_percentile=False):
+    """Test_KITTI.py:287-300: second forward on the flipped, x2/3-downscaled view; blend by normalised disparity.
+    device_percentile: the 95th percentile comes from dumps.percentile (exact, on the device, per sample) instead of the copy to the host and
+    np.percentile over the whole batch; the reference's loop runs at batch size 1, where the two are the same number."""
     B, C, H, W = input_view.shape
     up_fac = 2 / 3
     # F.interpolate(scale_factor=2/3) sizes the output as floor(in * scale) and (align_corners=True) samples at dst (in-1)/(out-1)
@@ -29,7 +32,11 @@ def ms_pp(input_view, pan_model, disp, min_disp, max_pix):
     dwn_flip_disp = pan_model(upscaled, min_disp, max_pix, ret_disp=True, ret_pan=False, ret_subocc=False)
     dwn_flip_disp = resize_planar(dwn_flip_disp, (H, W), bilinear=False, scale=1 / up_fac)
     dwn_flip_disp = hflip(dwn_flip_disp)
-    norm = disp / (np.percentile(disp.detach().cpu().numpy(), 95) + 1e-6)
+    if device_percentile:
+        from . import dumps
+        norm = disp / (dumps.percentile(disp, 95.0).view(-1, 1, 1, 1) + 1e-6)
+    else:
+        norm = disp / (np.percentile(disp.detach().cpu().numpy(), 95) + 1e-6)
     norm[norm > 1] = 1
     return (1 - norm) * disp + norm * dwn_flip_disp
 
@@ -40,13 +47,27 @@ def flip_post_process(input_view, pan_model, disp, min_disp, max_pix):
     return (disp + hflip(flip_disp)) / 2
 
 
+def dump_frame(writer, i, pan_model, left, disp, min_disp, max_pix):
+    """Frame `i` to disk through a dumps.FrameWriter (Test_KITTI.py:189-194,211-253).  The synthesised view and the occlusion masks come
+    from one more forward with ret_pan / ret_subocc, only where the writer wants them; the feature maps are the reference's
+    [local_normalization(input), maskL, maskRL] (its `dispr / 100` is not an output of this model's forward)."""
+    from . import dumps
+    pan = feats = None
+    if writer.needs_views:
+        pan, _, mask_l, mask_rl = pan_model(left, min_disp, max_pix, ret_disp=True, ret_subocc=True, ret_pan=True)
+        feats = [dumps.local_normalization(left), mask_l, mask_rl]
+    writer.write(i, left, disp, pan=pan, feats=feats)
+
+
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
-             print_freq=10, log=print, with_metrics=True):
+             print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
     datasets.StereoValDataset; gt is a disparity map (Kitti2015) or a depth map (Eigen split, listdataset_test.py:43-46 reads both
-    as uint16 / 256).  Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}."""
+    as uint16 / 256).  Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}.
+    writer: a dumps.FrameWriter -- every frame's outputs are also written to disk (:211-253), after the timed region and after the metrics;
+    where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp."""
     import time
     from . import datasets as DS
     from . import myUtils as utils
@@ -67,7 +88,7 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                 if post == "flip":
                     disp = flip_post_process(left, pan_model, disp, mn, mx)
                 elif post == "ms_pp":
-                    disp = ms_pp(left, pan_model, disp, mn, mx)
+                    disp = ms_pp(left, pan_model, disp, mn, mx, device_percentile)
                 torch.cuda.synchronize()
                 batch_time.update(time.time() - t0, 1)
                 if gt is not None and with_metrics:  # `-eval False`: forward and timing only (:255)
@@ -79,6 +100,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                     else:  # Eigen split: :258-263
                         gt_depth, pred_depth = utils.disps_to_depths_kitti(t_np, p_np)
                     kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
+                if writer is not None:
+                    dump_frame(writer, n, pan_model, left, disp, mn, mx)
                 n += 1
             if log is not None and i % print_freq == 0:
                 log('Test: [{0}/{1}]\t Time {2}\t a1 {3:.4f}'.format(i, len(loader), batch_time, kitti.avg[4]))  # :273-275

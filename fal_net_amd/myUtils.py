@@ -1,5 +1,6 @@
 """The part of the reference's myUtils.py the hot path needs: checkpoint writer, meters, and the KITTI metric
-chain behind `abs_rel vs ref` (myUtils.py:10-13,59-110,177-277).  Host-side numpy, as in the reference."""
+chain behind `abs_rel vs ref` (myUtils.py:10-13,59-110,177-277).  Host-side numpy, as in the reference.  Also the validation scalars
+(get_mea / get_rmse / get_psnr, :123-172) and the point cloud (:339-394), whose vertices come from the kernel behind fal_net_amd/dumps.py."""
 import os
 import shutil
 
@@ -66,6 +67,39 @@ def get_rmse(output_right, label_right, mean=(0.411, 0.432, 0.45)):
     out = ((output_right + shift) * 255).clamp(0, 255)
     lab = (label_right + shift) * 255
     return torch.mean((out - lab) ** 2) ** 0.5
+
+
+def _to_8bit(output_right, label_right, mean):
+    shift = torch.tensor(mean, device=output_right.device, dtype=output_right.dtype).view(1, 3, 1, 1)
+    return ((output_right + shift) * 255).clamp(0, 255), (label_right + shift) * 255
+
+
+def get_mea(output_right, label_right, mean=(0.411, 0.432, 0.45)):
+    """Mean absolute error of the synthesised view in 8-bit units (myUtils.py:123-135)."""
+    out, lab = _to_8bit(output_right, label_right, mean)
+    return torch.mean(torch.abs(out - lab))
+
+
+def get_psnr(output_right, label_right, mean=(0.411, 0.432, 0.45)):
+    """PSNR of the synthesised view, prediction rounded to 8-bit levels (myUtils.py:153-172: one RMSE over the whole batch)."""
+    out, lab = _to_8bit(output_right, label_right, mean)
+    rmse = torch.sqrt(torch.mean((out.round() - lab) ** 2))
+    return torch.mean(20 * torch.log10(255 / rmse))
+
+
+def get_point_cloud(img, disp):
+    """myUtils.py:339-373: `img` is RGB in 0..255, `disp` in pixels -> (B, 6, H W) rows x, z, -y, r, g, b on the input's device, computed by
+    the point-cloud kernel (fal_net_amd.dumps.point_cloud).  KeyError on a width that is not a KITTI width, as in the reference."""
+    from . import dumps
+    w = disp.shape[3]
+    return dumps.point_cloud(img, disp, focal=width_to_focal[w], baseline=width_to_baseline[w], mean=(0.0, 0.0, 0.0), rgb_scale=1.0)
+
+
+def save_point_cloud(pc, file_name, ply_format="ascii"):
+    """myUtils.py:378-394: `pc` = (6, n) array -> PLY.  The default is the reference's ASCII file; ply_format='binary' writes the same vertices
+    as binary_little_endian records."""
+    from . import dumps
+    dumps.save_ply(file_name, planar=pc, ply_format=ply_format)
 
 
 def get_n_params(model):

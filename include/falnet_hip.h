@@ -520,6 +520,40 @@ int falnet_spin(int microseconds, void* stream);
  * 2048 * 4 * iters * 16 * 16384.  bench.py's `roofline.sustained_mfma` (measurement only: no step launches it); `out` is never written on finite data. */
 int falnet_mfma_probe(const void* ab, float* out, int iters, int dtype, void* stream);
 
+/* ---- test-time outputs (csrc/dump.hip; Test_KITTI.py:211-253,303-317, myUtils.py:339-373) ----------------------------------------------
+ * Inputs are planar f32 (B, C, H, W) as the model returns them; `mean_*` is the RGB mean the loader subtracted (0.411, 0.432, 0.45).  Byte outputs
+ * are written as whole 32-bit words: the output pointer is 4-byte aligned and its ALLOCATION is rounded up to a multiple of 4 bytes (the pad
+ * bytes are written 0).  The f32 arithmetic is the host's, operation by operation (correctly rounded division, no fused multiply-add), so the
+ * 8-bit outputs equal numpy's byte for byte.  None of these is replayable (falnet_replay_op_index: -1).
+ *
+ * Exact q-th percentile (0 <= q <= 100) of each of the B samples of x (n_per_sample contiguous floats each), numpy's default 'linear' definition:
+ * position q/100 (n - 1), the two order statistics on either side found exactly (radix select on a monotone integer image of the floats, integer
+ * histograms: bit-identical from run to run), one interpolation in double.  NaN input is out of contract (a NaN sorts by its bit pattern); -0.0
+ * sorts below +0.0.  workspace: falnet_percentile_workspace_bytes(B) bytes, cleared by the call itself; after the call the words [4] and [5] of each
+ * sample's region (regions are workspace_bytes(B) / B bytes apart) hold the two order statistics as f32. */
+int64_t falnet_percentile_workspace_bytes(int B);
+int falnet_percentile_f32(const float* x, int64_t n_per_sample, int B, double q, float* out, void* workspace, void* stream);
+/* Test_KITTI.py:213-216 without the host: v = 256 clip(d / (p95[b] + 1e-6), 0, 1) in f32, k = min(rint(v), 255) (round half to even),
+ * out[b][y][x] = lut[k]; lut: 256 RGBA entries (fal_net_amd/plasma_lut.txt), out: (B, H, W, 4) u8; p95: B floats on the device */
+int falnet_disp_to_plasma_u8(const float* disp, const float* p95, const void* lut_rgba, void* out_rgba, int B, int H, int W, void* stream);
+/* Test_KITTI.py:229-241: planar (B, 3, H, W) -> interleaved (B, H, W, 3) u8, rint(255 (x + mean)) SATURATED to [0, 255] -- the one deliberate
+ * difference: the reference's astype(uint8) wraps an out-of-range value around */
+int falnet_image_to_u8(const float* x, float mean_r, float mean_g, float mean_b, void* out, int B, int H, int W, void* stream);
+/* Test_KITTI.py:248-253: rint(clip(255 |x|, 0, 255)) of n floats -> n bytes in the same order */
+int falnet_feature_to_u8(const float* x, void* out, int64_t n, void* stream);
+/* local_normalization, Test_KITTI.py:303-317, win = 3 only: img = x + mean, mu = avg_pool2d(img, 3, 1, 1), sigma = avg_pool2d((img - mu)^2, 3, 1, 1)^(1/2)
+ * (zero padding, divisor 9 at the borders too), out = (img - mu) / (sigma + 1e-7).  mu_out / sigma_out: NULL, or (B, 3, H, W) f32 that receive mu and
+ * sigma (the quotient is ill-conditioned where sigma ~ 0; tests compare its two parts) */
+int falnet_local_norm(const float* x, float mean_r, float mean_g, float mean_b, float* out, float* mu_out, float* sigma_out, int win, int B, int H, int W,
+                      void* stream);
+/* get_point_cloud, myUtils.py:339-373: z = focal baseline / (disp + 1e-4); u = j + 0.5, v = i + 0.5 (affine_grid with align_corners=False);
+ * x = (u - W/2) / focal z and y = (v - H/2) / focal z from the UNCAPPED z, then z clamped to [0, 200]; colour = (img + mean) * rgb_scale (255 for a
+ * model input; mean 0 and scale 1 for an image that is already 0..255, which is how the reference calls it).  out_planar: NULL or (B, 6, H W) f32, rows
+ * x, z, -y, r, g, b; out_packed: NULL or (B, H W) binary-PLY vertex records of 15 bytes (x, z, -y as little-endian f32; r, g, b as u8, truncated
+ * like the reference's int() and saturated).  At least one of the two. */
+int falnet_point_cloud(const float* img, float mean_r, float mean_g, float mean_b, float rgb_scale, const float* disp, double focal, double baseline,
+                       float* out_planar, void* out_packed, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
