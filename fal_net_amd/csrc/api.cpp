@@ -19,7 +19,7 @@ void falnet_set_error(const char* fmt, ...) {
 extern "C" int falnet_version(void) { return 600; }
 extern "C" const char* falnet_last_error(void) { return g_err; }
 
-// Deterministic mode (process-wide): see include/falnet_hip.h.  Read by the launchers of conv.hip / losses.hip.
+// Deterministic mode (process-wide): see include/falnet_hip.h.  Read by the launchers of conv.hip / wgrad.hip / losses.hip.
 static int g_deterministic = 0;
 int falnet_deterministic() { return g_deterministic; }
 int* falnet_replay_depth() {

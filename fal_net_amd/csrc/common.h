@@ -93,6 +93,30 @@ template <> struct H16<f16_t> {
 template <typename T> __device__ __forceinline__ unsigned pack16x2(float lo, float hi) {
     return (unsigned)H16<T>::bits(lo) | ((unsigned)H16<T>::bits(hi) << 16);
 }
+// eight consecutive channels as one value: 16-B (16-bit types) / 2 x 16-B (f32) loads and stores
+template <typename T> struct Vec8 {  // 16-bit operand types (bf16 / f16)
+    uint4 v;
+    __device__ __forceinline__ void load(const T* p) { v = *reinterpret_cast<const uint4*>(p); }
+    __device__ __forceinline__ void store(T* p) const { *reinterpret_cast<uint4*>(p) = v; }
+    __device__ __forceinline__ float get(int i) const {
+        const unsigned w = (&v.x)[i >> 1];
+        return (i & 1) ? H16<T>::hi(w) : H16<T>::lo(w);
+    }
+    __device__ __forceinline__ void set8(const float (&f)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) (&v.x)[i] = pack16x2<T>(f[2 * i], f[2 * i + 1]);
+    }
+};
+template <> struct Vec8<float> {
+    float4 a, b;
+    __device__ __forceinline__ void load(const float* p) { a = reinterpret_cast<const float4*>(p)[0]; b = reinterpret_cast<const float4*>(p)[1]; }
+    __device__ __forceinline__ void store(float* p) const { reinterpret_cast<float4*>(p)[0] = a; reinterpret_cast<float4*>(p)[1] = b; }
+    __device__ __forceinline__ float get(int i) const { return i < 4 ? (&a.x)[i] : (&b.x)[i - 4]; }
+    __device__ __forceinline__ void set8(const float (&f)[8]) {
+        a = make_float4(f[0], f[1], f[2], f[3]);
+        b = make_float4(f[4], f[5], f[6], f[7]);
+    }
+};
 // launch dispatch over the three operand types: X(T) is a statement using the type
 #define FALNET_DISPATCH_DTYPE(dtype, X)             \
     do {                                            \
@@ -129,4 +153,27 @@ __device__ __forceinline__ float block_sum(float v, float* red /* >= 16 floats o
         for (int i = 0; i < nw; ++i) r += red[i];
     }
     return r;
+}
+
+// entry lookup for the batched kernels: the block_begin column is fetched by n threads in parallel into LDS (a serial
+// walk of the global table cost ~0.5 us per entry per block)
+template <typename D>
+__device__ __forceinline__ int find_entry(const D* __restrict__ descs, int n, int* sh /* >= 64 ints */) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) sh[i] = descs[i].block_begin;
+    __syncthreads();
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int)blockIdx.x >= sh[mid]) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// argument check of one NHWC source of a convolution / weight-gradient descriptor
+static inline int check_src(const falnet_src_t& s, int kc, const char* who) {
+    FALNET_CHECK_ARG(s.ptr && s.C > 0 && s.C % kc == 0, "%s: source channels %d must be a positive multiple of %d", who, s.C, kc);
+    FALNET_CHECK_ARG(s.H > 0 && s.W > 0, "%s: empty source", who);
+    FALNET_CHECK_ARG((((uintptr_t)s.ptr) & 15) == 0, "%s: source pointer must be 16-B aligned", who);
+    return 0;
 }

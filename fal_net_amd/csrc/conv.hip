@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution on the gfx950 matrix cores (MFMA), forward / data-gradient / weight-gradient.
+// Implicit-GEMM convolution on the gfx950 matrix cores (MFMA), forward / data-gradient (weight gradients: wgrad.hip; weight packing: pack.hip).
 //
 // Replaces every cuDNN conv2d call site of the hot path (models/FAL_netB.py:38,45,55,73,75,127,190;
 // loss_functions.py:21-29) and their autograd.  One gather kernel serves forward and dgrad: the GEMM is
@@ -32,31 +32,8 @@ template <> struct KC<f16_t> { static constexpr int value = 32; };
 // The MFMA C/D layout puts one channel on each lane, so a direct store is 2 B (bf16) per lane: store-issue
 // bound.  Instead every wave stages one 32-row accumulator slab at a time through its private LDS area
 // (f32, pitch NT*32+4 floats) and then owns (row, 8-channel segment) pieces: bias / residual / activation /
-// activation-gradient are applied on 8 values and written with 16-B stores; addend / actout come in 16-B loads.
-template <typename T> struct Vec8 {  // 16-bit operand types (bf16 / f16)
-    uint4 v;
-    __device__ __forceinline__ void load(const T* p) { v = *reinterpret_cast<const uint4*>(p); }
-    __device__ __forceinline__ void store(T* p) const { *reinterpret_cast<uint4*>(p) = v; }
-    __device__ __forceinline__ float get(int i) const {
-        const unsigned w = (&v.x)[i >> 1];
-        return (i & 1) ? H16<T>::hi(w) : H16<T>::lo(w);
-    }
-    __device__ __forceinline__ void set8(const float (&f)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) (&v.x)[i] = pack16x2<T>(f[2 * i], f[2 * i + 1]);
-    }
-};
-template <> struct Vec8<float> {
-    float4 a, b;
-    __device__ __forceinline__ void load(const float* p) { a = reinterpret_cast<const float4*>(p)[0]; b = reinterpret_cast<const float4*>(p)[1]; }
-    __device__ __forceinline__ void store(float* p) const { reinterpret_cast<float4*>(p)[0] = a; reinterpret_cast<float4*>(p)[1] = b; }
-    __device__ __forceinline__ float get(int i) const { return i < 4 ? (&a.x)[i] : (&b.x)[i - 4]; }
-    __device__ __forceinline__ void set8(const float (&f)[8]) {
-        a = make_float4(f[0], f[1], f[2], f[3]);
-        b = make_float4(f[4], f[5], f[6], f[7]);
-    }
-};
-
+// activation-gradient are applied on 8 values and written with 16-B stores; addend / actout come in 16-B loads (common.h: Vec8).
+//
 // RowOff: functor row(0..31 of slab mt) -> element offset of the output pixel's channel 0, or -1
 // PoolOff (optional, MT even): slabs are consecutive image rows and slab rows consecutive columns; called for odd mt /
 // even row, returns the element offset of the 2x2-pooled pixel in p.pool_out or -1.  The horizontal neighbour lives in
@@ -1597,1266 +1574,7 @@ __global__ __launch_bounds__(CONV_THREADS, C3_OCC) void conv3x3_c3_kernel(const 
 }
 #undef C3_STAMP
 
-// ------------------------------------------------------------------------------------------ wgrad
-// dW[co, tap, ci] = sum_p G[p, co] * In[nbr(p, tap), ci]: both operands are pixel-major (the contraction
-// index is the slow one), so the LDS tiles are [pixel][channel] and the MFMA operands are read transposed:
-//   bf16: ds_read_b64_tr_b16 (two per 8-element fragment);  f32: one ds_read_b32 per lane (A[m][k]: m on lanes).
-// Workgroup = 64 couts x 64 cins for one (tap, pixel split); 4 waves 2x2, 32x32 each; 64 pixels per K step.
-#define WG_BM 64
-#define WG_BN 64
-#define WG_KP 64
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__global__ __launch_bounds__(CONV_THREADS) void wgrad_kernel(const falnet_wgrad_t p, int w_rows) {
-    constexpr int EPS = 16 / sizeof(T);
-    constexpr int ROW_ELEMS = 64;                          // channels per tile row
-    constexpr int SEGS = ROW_ELEMS / EPS;                  // 16-B segments per row (8 bf16 / 16 f32)
-    constexpr int PITCH = ROW_ELEMS * sizeof(T) + 16;      // bytes
-    constexpr int LOADS = WG_KP * SEGS / CONV_THREADS;     // per operand per thread (2 bf16 / 4 f32)
-    __shared__ __attribute__((aligned(16))) char lds[2 * 2 * WG_KP * PITCH];
-    auto Gbuf = [&](int b) -> char* { return lds + b * 2 * WG_KP * PITCH; };
-    auto Ibuf = [&](int b) -> char* { return lds + b * 2 * WG_KP * PITCH + WG_KP * PITCH; };
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ci0 = blockIdx.x * WG_BN;   // packed input-channel offset (over all sources)
-    const int co0 = blockIdx.y * WG_BM;
-    const int tap = blockIdx.z % p.ntaps, split = blockIdx.z / p.ntaps;
-    const int dy = p.tap_dy[tap], dx = p.tap_dx[tap];
-    const int c_first = p.src[0].C;  // packed channels [0, c_first) come from source 0, the rest from source 1
-
-    const int64_t M = (int64_t)p.B * p.TH * p.TW;
-    const int64_t per = ((M + p.nsplit - 1) / p.nsplit + WG_KP - 1) / WG_KP * WG_KP;
-    const int64_t pbeg = (int64_t)split * per, pend = pbeg + per < M ? pbeg + per : M;
-    const int niter = pbeg < pend ? (int)((pend - pbeg + WG_KP - 1) / WG_KP) : 0;
-
-    uint4 greg[LOADS], ireg[LOADS];
-    int64_t pcur = pbeg;
-    auto gload = [&]() {
-#pragma unroll
-        for (int i = 0; i < LOADS; ++i) {
-            const int idx = tid + i * CONV_THREADS;
-            const int row = idx / SEGS, seg = idx % SEGS;
-            const int64_t m = pcur + row;
-            uint4 g = make_uint4(0, 0, 0, 0), v = make_uint4(0, 0, 0, 0);
-            if (m < pend) {
-                if (co0 + seg * EPS < p.gC)
-                    g = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.gout) + m * p.gC + co0 + seg * EPS);
-                const int tx = (int)(m % p.TW), ty = (int)((m / p.TW) % p.TH), b = (int)(m / ((int64_t)p.TW * p.TH));
-                int vy = ty * p.isy + dy, vx = tx * p.isx + dx;
-                const int cpk = ci0 + seg * EPS;  // packed channel of this 16-B segment
-                const falnet_src_t& S = p.src[cpk < c_first ? 0 : 1];
-                const int cloc = cpk < c_first ? cpk : cpk - c_first;
-                if (vy >= 0 && vy < p.IH && vx >= 0 && vx < p.IW && cpk < p.cin_total) {
-                    if ((S.H != p.IH) || (S.W != p.IW)) {
-                        vy = (2 * S.H == p.IH) ? (vy >> 1) : (int)(((int64_t)vy * S.H) / p.IH);
-                        vx = (2 * S.W == p.IW) ? (vx >> 1) : (int)(((int64_t)vx * S.W) / p.IW);
-                    }
-                    v = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(S.ptr) + (int64_t)b * S.sb +
-                                                        (int64_t)vy * S.sy + (int64_t)vx * S.sx + cloc);
-                }
-            }
-            greg[i] = g;
-            ireg[i] = v;
-        }
-        pcur += WG_KP;
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < LOADS; ++i) {
-            const int idx = tid + i * CONV_THREADS;
-            const int row = idx / SEGS, seg = idx % SEGS;
-            *reinterpret_cast<uint4*>(Gbuf(buf) + row * PITCH + seg * 16) = greg[i];
-            *reinterpret_cast<uint4*>(Ibuf(buf) + row * PITCH + seg * 16) = ireg[i];
-        }
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-
-    if (niter > 0) {
-        gload();
-        lstore(0);
-    }
-    __syncthreads();
-    for (int it = 0; it < niter; ++it) {
-        const int cur = it & 1;
-        if (it + 1 < niter) gload();
-        const char* G = Gbuf(cur);
-        const char* I = Ibuf(cur);
-        if constexpr (sizeof(T) == 2) {
-            // lane group g16 = lane>>4: k-half = g16>>1, 16-channel block = g16&1; lane i=lane&15 supplies row q=i>>2, cols 4*(i&3)
-            const int i16 = lane & 15, g16 = lane >> 4;
-            const int kh = g16 >> 1, cb = g16 & 1, q = i16 >> 2, pc = i16 & 3;
-#pragma unroll
-            for (int ks = 0; ks < WG_KP / 16; ++ks) {
-                const int krow = ks * 16 + kh * 8 + q;
-                const int acol = (wm * 32 + cb * 16 + pc * 4) * 2, bcol = (wn * 32 + cb * 16 + pc * 4) * 2;
-                typedef s16x4 __attribute__((address_space(3))) * lds_v4;
-                s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(G + krow * PITCH + acol));
-                s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(G + (krow + 4) * PITCH + acol));
-                s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(I + krow * PITCH + bcol));
-                s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(I + (krow + 4) * PITCH + bcol));
-                typedef short s16x8 __attribute__((ext_vector_type(8)));
-                s16x8 av = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                s16x8 bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                acc = H16<T>::mma(__builtin_bit_cast(s16x8_t, av), __builtin_bit_cast(s16x8_t, bv), acc);
-            }
-        } else {
-            const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-            for (int ks = 0; ks < WG_KP / 2; ++ks) {
-                const float a = *reinterpret_cast<const float*>(G + (ks * 2 + h) * PITCH + (wm * 32 + r) * 4);
-                const float b = *reinterpret_cast<const float*>(I + (ks * 2 + h) * PITCH + (wn * 32 + r) * 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-            }
-        }
-        if (it + 1 < niter) lstore(cur ^ 1);
-        __syncthreads();
-    }
-    // partial[split][tap][co][ci]
-    const int r = lane & 31, h = lane >> 5;
-    const int ci = ci0 + wn * 32 + r;
-    if (ci < p.cin_total) {
-        float* dst = p.partial + (((int64_t)split * p.ntaps + tap) * w_rows) * p.cin_total;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int co = co0 + wm * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
-            if (co < w_rows) dst[(int64_t)co * p.cin_total + ci] = acc[j];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------ wgrad, halo-patch form
-// Dense 3x3 stride-1 layers (the bulk of the weight-gradient FLOPs): a workgroup owns a 32x32 (cout x cin)
-// channel block for ALL nine taps and walks a range of 4x32-position patches.  Per patch the gout rows
-// [128 px][32 cout] and the input halo [6x34 px][32 cin] are staged ONCE in LDS (the per-tap kernel re-read both
-// nine times); wave w contracts image row w of the patch (K = 32 positions) into its nine 32x32 accumulators,
-// operands read transposed (bf16: ds_read_b64_tr_b16) as in wgrad_kernel.  The four waves' accumulators are
-// summed through LDS at the end and the workgroup writes ONE f32 slab [9][32][32] into
-// partial[split][tap][co][ci].  Next patch is prefetched into registers behind the MFMAs.
-#define WP_TH 4
-#define WP_TW 32
-#define WP_PW (WP_TW + 2)
-#define WP_NPIX ((WP_TH + 2) * WP_PW)
-
-#define WP_THREADS 192  // three waves: wave w owns the tap row dy = w-1 (taps 3w..3w+2)
-
-// Bias gradient from the gout tile a weight-gradient workgroup has in LDS ([plane][pixel][32 channels], zero-filled outside the
-// image): every thread owns one 16-B channel segment and strides over the tile's pixels, accumulating in registers across
-// all patches of the workgroup; bias_grad_flush sums the pixel groups through LDS and issues one atomic per channel.
-template <typename T, int COT, int NTHR>
-__device__ __forceinline__ void bias_grad_accumulate(const char* G, int tid, float (&bsum)[16 / (int)sizeof(T)]) {
-    constexpr int EPS = 16 / (int)sizeof(T), SEGS = 32 / EPS, NSEG = SEGS * COT, PSTEP = NTHR / NSEG;
-    static_assert(NTHR % NSEG == 0, "threads map evenly onto channel segments");
-    constexpr int NPIXT = WP_TH * WP_TW, G_PLANE = NPIXT * 32 * (int)sizeof(T);
-    const int sg = tid % NSEG, pg = tid / NSEG;
-    const char* base = G + (sg / SEGS) * G_PLANE + (sg % SEGS) * 16;
-    for (int px = pg; px < NPIXT; px += PSTEP) {
-        const uint4 v = *reinterpret_cast<const uint4*>(base + px * 32 * (int)sizeof(T));
-        if constexpr (sizeof(T) == 2) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const unsigned w = (&v.x)[i];
-                bsum[2 * i] += H16<T>::lo(w);
-                bsum[2 * i + 1] += H16<T>::hi(w);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bsum[i] += __uint_as_float((&v.x)[i]);
-        }
-    }
-}
-template <typename T, int COT, int NTHR>
-__device__ __forceinline__ void bias_grad_flush(float* lds_f /* >= NTHR * EPS floats, all waves past their last LDS use */, int tid,
-                                                const float (&bsum)[16 / (int)sizeof(T)], float* db, int co0, int gC) {
-    constexpr int EPS = 16 / (int)sizeof(T), SEGS = 32 / EPS, NSEG = SEGS * COT, PSTEP = NTHR / NSEG;
-#pragma unroll
-    for (int i = 0; i < EPS; ++i) lds_f[tid * EPS + i] = bsum[i];
-    __syncthreads();
-    if (tid < NSEG * EPS) {
-        const int sg = tid / EPS, i = tid % EPS;
-        float t = 0.f;
-        for (int pg = 0; pg < PSTEP; ++pg) t += lds_f[(pg * NSEG + sg) * EPS + i];
-        const int co = co0 + (sg / SEGS) * 32 + (sg % SEGS) * EPS + i;
-        if (co < gC) atomicAdd(db + co, t);
-    }
-}
-
-// CIT x COT = 32-channel tiles per workgroup along cin / cout (1x1, or 2x2 for bf16 layers with >= 64 channels on both
-// sides): every wave then owns 3 taps x CIT x COT accumulator tiles, and one A (gout) fragment feeds 3*CIT MFMAs, one B
-// (input) fragment COT of them -- half the LDS reads and half the global bytes per MFMA of the 1x1 form, whose ~2.7
-// transposed reads per MFMA and 21 KB per 72 MFMAs sit on the LDS / CU load path.  Channel planes are stored separately
-// ([plane][pixel][32 channels], 64-B rows) so the transposed-read addressing is the same for every plane.
-template <typename T, int CIT, int COT>
-__global__ __launch_bounds__(WP_THREADS) void wgrad3x3_patch_kernel(const falnet_wgrad_t p, int w_rows, int tiles_x, int tiles_y,
-                                                                    int patches_per_split) {
-    constexpr int EPS = 16 / (int)sizeof(T);
-    constexpr int ROWB_ = 32 * (int)sizeof(T);      // bytes of 32 channels
-    constexpr int SEGS = ROWB_ / 16;                // 4 (bf16) / 8 (f32)
-    // no row padding: a ds_read_b64_tr_b16 32-lane half reads 4 rows x 64 B = exactly the 64 banks once
-    constexpr int PITCH = ROWB_;
-    constexpr int G_PLANE = WP_TH * WP_TW * PITCH, I_PLANE = WP_NPIX * PITCH;
-    constexpr int G_BYTES = COT * G_PLANE, I_BYTES = CIT * I_PLANE;
-    constexpr int G_LOADS = WP_TH * WP_TW * SEGS * COT, I_LOADS = WP_NPIX * SEGS * CIT;
-    constexpr int G_SLOTS = (G_LOADS + WP_THREADS - 1) / WP_THREADS;
-    constexpr int I_SLOTS = (I_LOADS + WP_THREADS - 1) / WP_THREADS;
-    __shared__ __attribute__((aligned(16))) char lds[2 * (G_BYTES + I_BYTES)];
-    auto Gbuf = [&](int b) -> char* { return lds + b * (G_BYTES + I_BYTES); };
-    auto Ibuf = [&](int b) -> char* { return lds + b * (G_BYTES + I_BYTES) + G_BYTES; };
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ci0 = blockIdx.x * 32 * CIT, co0 = blockIdx.y * 32 * COT, split = blockIdx.z;
-    const int c_first = p.src[0].C;
-    // per cin tile: source, channel offset inside it, resize flags (workgroup-uniform; a 64-channel block may straddle
-    // the two sources of a fused concat)
-    const T* t_ptr[CIT];
-    int64_t t_sb[CIT], t_sy[CIT], t_sx[CIT];
-    int t_H[CIT], t_W[CIT];
-    bool t_ok[CIT];
-#pragma unroll
-    for (int t = 0; t < CIT; ++t) {
-        const int c = ci0 + 32 * t;
-        const bool second = c >= c_first;
-        t_ok[t] = c < p.cin_total;
-        t_ptr[t] = reinterpret_cast<const T*>(second ? p.src[1].ptr : p.src[0].ptr) + (second ? c - c_first : c);
-        t_sb[t] = second ? p.src[1].sb : p.src[0].sb;
-        t_sy[t] = second ? p.src[1].sy : p.src[0].sy;
-        t_sx[t] = second ? p.src[1].sx : p.src[0].sx;
-        t_H[t] = second ? p.src[1].H : p.src[0].H;
-        t_W[t] = second ? p.src[1].W : p.src[0].W;
-    }
-    const int npatch = p.B * tiles_x * tiles_y;
-    const int pbeg = split * patches_per_split, pend = min(pbeg + patches_per_split, npatch);
-
-    // halo slots: (row, col) of the 6x34 patch per slot (division by 34 hoisted out of the patch loop); with CIT = 2 the
-    // eight 16-B segments of a pixel are consecutive lanes (one full 128-B line when both tiles share a source)
-    short i_row[I_SLOTS], i_col[I_SLOTS];
-#pragma unroll
-    for (int u = 0; u < I_SLOTS; ++u) {
-        const int pix = (tid + u * WP_THREADS) / (SEGS * CIT);
-        i_row[u] = (short)(pix / WP_PW);
-        i_col[u] = (short)(pix % WP_PW);
-    }
-
-    // Interior patches (the vast majority) take a fast path: every slot's element offset relative to the patch origin is
-    // loop-invariant (also through an exact 2x nearest upsampling: origins are even), so a load is one 64-bit add -- the
-    // general path costs ~25 VALU per load, i.e. ~8 VALU per MFMA of this kernel (PMC), as much issue time as the MFMAs.
-    int g_off[G_SLOTS], i_off[I_SLOTS];
-    bool fast_ok = true;  // every tile's source is at the launch size or exactly half of it
-#pragma unroll
-    for (int t = 0; t < CIT; ++t)
-        fast_ok = fast_ok && (t_H[t] == p.IH || 2 * t_H[t] == p.IH) && (t_W[t] == p.IW || 2 * t_W[t] == p.IW) &&
-                  (int64_t)p.B * t_sb[t] < (1ll << 31);
-    fast_ok = fast_ok && (int64_t)p.B * p.TH * p.TW * p.gC < (1ll << 31) && co0 + 32 * COT <= p.gC && ci0 + 32 * CIT <= p.cin_total;
-#pragma unroll
-    for (int u = 0; u < G_SLOTS; ++u) {
-        const int idx = tid + u * WP_THREADS;
-        const int seg = idx % (SEGS * COT), pix = idx / (SEGS * COT);
-        g_off[u] = ((pix / WP_TW) * p.TW + pix % WP_TW) * p.gC + seg * EPS;
-    }
-#pragma unroll
-    for (int u = 0; u < I_SLOTS; ++u) {
-        const int idx = tid + u * WP_THREADS;
-        const int seg8 = idx % (SEGS * CIT), seg = seg8 % SEGS;
-        const bool t1 = CIT > 1 && seg8 >= SEGS;
-        const int hs = (t1 ? t_H[CIT - 1] : t_H[0]) != p.IH ? 1 : 0, ws = (t1 ? t_W[CIT - 1] : t_W[0]) != p.IW ? 1 : 0;
-        const int ry = (i_row[u] - 1) >> hs, rx = (i_col[u] - 1) >> ws;  // arithmetic shifts: -1 stays -1
-        i_off[u] = (int)(ry * (t1 ? t_sy[CIT - 1] : t_sy[0]) + rx * (t1 ? t_sx[CIT - 1] : t_sx[0])) + seg * EPS;
-    }
-    struct Regs { uint4 g[G_SLOTS]; uint4 i[I_SLOTS]; };
-    auto gload = [&](int patch, Regs& R) {
-        int q = patch;
-        const int tix = q % tiles_x;
-        q /= tiles_x;
-        const int tiy = q % tiles_y;
-        const int b = q / tiles_y;
-        const int y0 = tiy * WP_TH, x0 = tix * WP_TW;
-        const T* gbase = reinterpret_cast<const T*>(p.gout) + ((int64_t)b * p.TH * p.TW) * p.gC + co0;
-        if (fast_ok && y0 >= 1 && x0 >= 1 && y0 + WP_TH + 1 <= p.IH && x0 + WP_TW + 1 <= p.IW && y0 + WP_TH <= p.TH && x0 + WP_TW <= p.TW) {
-            const T* gb = gbase + ((int64_t)y0 * p.TW + x0) * p.gC;
-#pragma unroll
-            for (int u = 0; u < G_SLOTS; ++u) {
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (tid + u * WP_THREADS < G_LOADS) v = *reinterpret_cast<const uint4*>(gb + g_off[u]);
-                R.g[u] = v;
-            }
-            const T* ib[CIT];
-#pragma unroll
-            for (int t = 0; t < CIT; ++t) {
-                const int hs = t_H[t] != p.IH ? 1 : 0, ws = t_W[t] != p.IW ? 1 : 0;
-                ib[t] = t_ptr[t] + (int64_t)b * t_sb[t] + (int64_t)(y0 >> hs) * t_sy[t] + (int64_t)(x0 >> ws) * t_sx[t];
-            }
-#pragma unroll
-            for (int u = 0; u < I_SLOTS; ++u) {
-                const int idx = tid + u * WP_THREADS;
-                const bool t1 = CIT > 1 && idx % (SEGS * CIT) >= SEGS;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (idx < I_LOADS) v = *reinterpret_cast<const uint4*>((t1 ? ib[CIT - 1] : ib[0]) + i_off[u]);
-                R.i[u] = v;
-            }
-            return;
-        }
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg = idx % (SEGS * COT), pix = idx / (SEGS * COT);
-            const int y = y0 + pix / WP_TW, x = x0 + pix % WP_TW;  // WP_TW = 32: shifts
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < G_LOADS && y < p.TH && x < p.TW && co0 + seg * EPS < p.gC)
-                v = *reinterpret_cast<const uint4*>(gbase + ((int64_t)y * p.TW + x) * p.gC + seg * EPS);
-            R.g[u] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < I_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg8 = idx % (SEGS * CIT), t = seg8 / SEGS, seg = seg8 % SEGS;
-            const bool t1 = CIT > 1 && t == 1;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            int vy = y0 - 1 + i_row[u], vx = x0 - 1 + i_col[u];
-            if (idx < I_LOADS && (t1 ? t_ok[CIT - 1] : t_ok[0]) && vy >= 0 && vy < p.IH && vx >= 0 && vx < p.IW) {
-                const int sH = t1 ? t_H[CIT - 1] : t_H[0], sW = t1 ? t_W[CIT - 1] : t_W[0];
-                if (sH != p.IH) vy = (2 * sH == p.IH) ? (vy >> 1) : (int)(((int64_t)vy * sH) / p.IH);
-                if (sW != p.IW) vx = (2 * sW == p.IW) ? (vx >> 1) : (int)(((int64_t)vx * sW) / p.IW);
-                const T* ib = t1 ? t_ptr[CIT - 1] : t_ptr[0];
-                v = *reinterpret_cast<const uint4*>(ib + (int64_t)b * (t1 ? t_sb[CIT - 1] : t_sb[0]) + (int64_t)vy * (t1 ? t_sy[CIT - 1] : t_sy[0]) +
-                                                    (int64_t)vx * (t1 ? t_sx[CIT - 1] : t_sx[0]) + seg * EPS);
-            }
-            R.i[u] = v;
-        }
-    };
-    auto lstore = [&](int buf, const Regs& R) {
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg8 = idx % (SEGS * COT), pix = idx / (SEGS * COT);
-            if (idx < G_LOADS) *reinterpret_cast<uint4*>(Gbuf(buf) + (seg8 / SEGS) * G_PLANE + (pix * SEGS + seg8 % SEGS) * 16) = R.g[u];
-        }
-#pragma unroll
-        for (int u = 0; u < I_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg8 = idx % (SEGS * CIT), pix = idx / (SEGS * CIT);
-            if (idx < I_LOADS) *reinterpret_cast<uint4*>(Ibuf(buf) + (seg8 / SEGS) * I_PLANE + (pix * SEGS + seg8 % SEGS) * 16) = R.i[u];
-        }
-    };
-
-    f32x16 acc[3][CIT][COT];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int a = 0; a < CIT; ++a)
-#pragma unroll
-            for (int c = 0; c < COT; ++c)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) acc[t][a][c][j] = 0.f;
-
-    auto compute = [&](int cur) {
-        const char* G = Gbuf(cur);
-        const char* I = Ibuf(cur) + wave * (WP_PW * PITCH);   // tap row dy = wave-1: halo rows shifted by `wave`
-        if constexpr (sizeof(T) == 2) {
-            const int i16 = lane & 15, g16 = lane >> 4;
-            const int kh = g16 >> 1, cb = g16 & 1, q = i16 >> 2, pc = i16 & 3;
-            typedef s16x4 __attribute__((address_space(3))) * lds_v4;
-            const int lane_off = (kh * 8 + q) * PITCH + (cb * 16 + pc * 4) * 2;
-            const char* gl = G + lane_off;
-            const char* il = I + lane_off;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {  // K = 128 positions: image row ks>>1 of the patch, 16-position half ks&1
-                const int goff = ks * 16 * PITCH;
-                s16x8_t av[COT];
-#pragma unroll
-                for (int c = 0; c < COT; ++c) {
-                    s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + c * G_PLANE + goff));
-                    s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + c * G_PLANE + goff + 4 * PITCH));
-                    av[c] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-#pragma unroll
-                for (int a = 0; a < CIT; ++a)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const int ioff = a * I_PLANE + ((ks >> 1) * WP_PW + (ks & 1) * 16 + dx) * PITCH;
-                        s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(il + ioff));
-                        s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(il + ioff + 4 * PITCH));
-                        const s16x8_t bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                        for (int c = 0; c < COT; ++c) acc[dx][a][c] = H16<T>::mma(av[c], bv, acc[dx][a][c]);
-                    }
-            }
-        } else {
-            const int r = lane & 31, h = lane >> 5;
-#pragma unroll 8
-            for (int ks = 0; ks < 64; ++ks) {  // 2 positions per MFMA
-                const int pos = ks * 2 + h;     // 0..127 inside the patch
-                float av[COT];
-#pragma unroll
-                for (int c = 0; c < COT; ++c) av[c] = *reinterpret_cast<const float*>(G + c * G_PLANE + pos * PITCH + r * 4);
-                const int ipix = (pos >> 5) * WP_PW + (pos & 31);
-#pragma unroll
-                for (int a = 0; a < CIT; ++a)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const float bb = *reinterpret_cast<const float*>(I + a * I_PLANE + (ipix + dx) * PITCH + r * 4);
-#pragma unroll
-                        for (int c = 0; c < COT; ++c) acc[dx][a][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c], bb, acc[dx][a][c], 0, 0, 0);
-                    }
-            }
-        }
-    };
-
-    // distance-1 prefetch (a second register set for distance 2 costs a wave of occupancy and measured slower)
-    Regs R0;
-    if (pbeg < pend) {
-        gload(pbeg, R0);
-        lstore(0, R0);
-    }
-    __syncthreads();
-    const bool do_bias = p.bias_grad != nullptr && blockIdx.x == 0;  // one cin tile per cout slice sums the bias gradient
-    float bsum[EPS];
-#pragma unroll
-    for (int i = 0; i < EPS; ++i) bsum[i] = 0.f;
-    for (int patch = pbeg; patch < pend; ++patch) {
-        const int cur = (patch - pbeg) & 1;
-        if (patch + 1 < pend) gload(patch + 1, R0);
-        compute(cur);
-        if (do_bias) bias_grad_accumulate<T, COT, WP_THREADS>(Gbuf(cur), tid, bsum);
-        if (patch + 1 < pend) lstore(cur ^ 1, R0);
-        __syncthreads();
-    }
-    if (do_bias) bias_grad_flush<T, COT, WP_THREADS>(reinterpret_cast<float*>(lds), tid, bsum, p.bias_grad, co0, p.cout);
-    // every wave owns its three taps: no cross-wave reduction
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int a = 0; a < CIT; ++a) {
-        const int ci = ci0 + 32 * a + r;
-        if (ci < p.cin_total) {
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                float* dst = p.partial + (((int64_t)split * 9 + wave * 3 + dx) * w_rows) * p.cin_total;
-#pragma unroll
-                for (int c = 0; c < COT; ++c)
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        const int co = co0 + 32 * c + (j & 3) + 8 * (j >> 2) + 4 * h;
-                        if (co < w_rows) dst[(int64_t)co * p.cin_total + ci] = acc[dx][a][c][j];
-                    }
-            }
-        }
-    }
-}
-
-// Stride-2 3x3 weight gradient (encoder convs conv1..conv6, FAL_netB.py:101-111), bf16: the same wave-per-tap-row scheme
-// as the dense kernel on a 4x32 block of OUTPUT positions; the (2*4+1)x(2*32+1) input region is loaded as whole contiguous
-// rows and de-interleaved by row / column parity into four LDS planes (even/odd rows x even/odd columns), so that the
-// pixels tap (ky,kx) needs for 16 consecutive outputs (2x+kx-1: stride 2 in the image) are 16 CONSECUTIVE rows of one
-// plane -- the transposed reads and their conflict-free 64-B pitch are exactly those of the dense kernel.
-//   tap ky: rows 2y+ky-1 -> ky=1: odd region rows (index y), ky=0 / 2: even region rows (index y / y+1); columns alike.
-// (The per-tap gather kernel it replaces ran these layers at 65-130 TFLOP/s on the longest chain of the backward pass.)
-#define WS2_RH (2 * WP_TH + 1)   // region rows
-#define WS2_RW (2 * WP_TW + 1)   // region columns
-template <typename T, int COT>
-__global__ __launch_bounds__(WP_THREADS, 2) void wgrad3x3_s2_kernel(const falnet_wgrad_t p, int w_rows, int tiles_x, int tiles_y,
-                                                                 int patches_per_split) {
-    constexpr int EPS = 8, SEGS = 4, PITCH = 64;
-    constexpr int NE_R = WP_TH + 1, NO_R = WP_TH, NE_C = WP_TW + 1, NO_C = WP_TW;  // even / odd region rows and columns
-    // plane (row parity, column parity) -> pixel offset of its first pixel; E = even region index
-    constexpr int P_EE = 0, P_EO = P_EE + NE_R * NE_C, P_OE = P_EO + NE_R * NO_C, P_OO = P_OE + NO_R * NE_C, I_PIX = P_OO + NO_R * NO_C;
-    static_assert(I_PIX == WS2_RH * WS2_RW, "the four planes tile the region");
-    constexpr int G_PLANE = WP_TH * WP_TW * PITCH;
-    constexpr int G_BYTES = COT * G_PLANE, I_BYTES = I_PIX * PITCH;
-    constexpr int G_LOADS = WP_TH * WP_TW * SEGS * COT, I_LOADS = I_PIX * SEGS;
-    constexpr int G_SLOTS = (G_LOADS + WP_THREADS - 1) / WP_THREADS, I_SLOTS = (I_LOADS + WP_THREADS - 1) / WP_THREADS;
-    // ONE LDS buffer (54 KB with COT = 2) + register prefetch of the next block: two workgroups per CU overlap each other
-    __shared__ __attribute__((aligned(16))) char lds[G_BYTES + I_BYTES];
-    auto Gbuf = [&](int) -> char* { return lds; };
-    auto Ibuf = [&](int) -> char* { return lds + G_BYTES; };
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32 * COT, split = blockIdx.z;
-    const int c_first = p.src[0].C;
-    const bool second = ci0 >= c_first;
-    const T* s_ptr = reinterpret_cast<const T*>(second ? p.src[1].ptr : p.src[0].ptr) + (second ? ci0 - c_first : ci0);
-    const int64_t s_sb = second ? p.src[1].sb : p.src[0].sb, s_sy = second ? p.src[1].sy : p.src[0].sy, s_sx = second ? p.src[1].sx : p.src[0].sx;
-    const int npatch = p.B * tiles_x * tiles_y;
-    const int pbeg = split * patches_per_split, pend = min(pbeg + patches_per_split, npatch);
-
-    // region slots: (row, column, 16-B segment) -> LDS offset inside the parity plane (loop-invariant)
-    short i_row[I_SLOTS], i_col[I_SLOTS];
-    int i_lds[I_SLOTS];
-#pragma unroll
-    for (int u = 0; u < I_SLOTS; ++u) {
-        const int idx = tid + u * WP_THREADS;
-        const int seg = idx % SEGS, pix = idx / SEGS;
-        const int r = pix / WS2_RW, c = pix % WS2_RW;
-        i_row[u] = (short)r;
-        i_col[u] = (short)c;
-        const int base = (r & 1) ? ((c & 1) ? P_OO : P_OE) : ((c & 1) ? P_EO : P_EE);
-        const int pw = (c & 1) ? NO_C : NE_C;
-        i_lds[u] = idx < I_LOADS ? (base + (r >> 1) * pw + (c >> 1)) * PITCH + seg * 16 : -1;
-    }
-    struct Regs { uint4 g[G_SLOTS]; uint4 i[I_SLOTS]; };
-    auto gload = [&](int patch, Regs& R) {
-        int q = patch;
-        const int tix = q % tiles_x;
-        q /= tiles_x;
-        const int tiy = q % tiles_y;
-        const int b = q / tiles_y;
-        const int y0 = tiy * WP_TH, x0 = tix * WP_TW;
-        const T* gbase = reinterpret_cast<const T*>(p.gout) + ((int64_t)b * p.TH * p.TW) * p.gC + co0;
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg = idx % (SEGS * COT), pix = idx / (SEGS * COT);
-            const int y = y0 + pix / WP_TW, x = x0 + pix % WP_TW;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < G_LOADS && y < p.TH && x < p.TW && co0 + seg * EPS < p.gC)
-                v = *reinterpret_cast<const uint4*>(gbase + ((int64_t)y * p.TW + x) * p.gC + seg * EPS);
-            R.g[u] = v;
-        }
-        const T* ibase = s_ptr + (int64_t)b * s_sb;
-#pragma unroll
-        for (int u = 0; u < I_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            const int vy = 2 * y0 - 1 + i_row[u], vx = 2 * x0 - 1 + i_col[u];
-            if (idx < I_LOADS && vy >= 0 && vy < p.IH && vx >= 0 && vx < p.IW)
-                v = *reinterpret_cast<const uint4*>(ibase + (int64_t)vy * s_sy + (int64_t)vx * s_sx + (idx % SEGS) * EPS);
-            R.i[u] = v;
-        }
-    };
-    auto lstore = [&](int buf, const Regs& R) {
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WP_THREADS;
-            const int seg8 = idx % (SEGS * COT), pix = idx / (SEGS * COT);
-            if (idx < G_LOADS) *reinterpret_cast<uint4*>(Gbuf(buf) + (seg8 / SEGS) * G_PLANE + (pix * SEGS + seg8 % SEGS) * 16) = R.g[u];
-        }
-#pragma unroll
-        for (int u = 0; u < I_SLOTS; ++u)
-            if (i_lds[u] >= 0) *reinterpret_cast<uint4*>(Ibuf(buf) + i_lds[u]) = R.i[u];
-    };
-
-    f32x16 acc[3][COT];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int c = 0; c < COT; ++c)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[t][c][j] = 0.f;
-    const int i16 = lane & 15, g16 = lane >> 4;
-    const int kh = g16 >> 1, cb = g16 & 1, q4 = i16 >> 2, pc = i16 & 3;
-    typedef s16x4 __attribute__((address_space(3))) * lds_v4;
-    const int lane_off = (kh * 8 + q4) * PITCH + (cb * 16 + pc * 4) * 2;
-    // wave = ky: region-row parity and row shift inside the plane
-    const bool odd_rows = wave == 1;
-    const int row_shift = wave == 2 ? 1 : 0;
-
-    auto compute = [&](int cur) {
-        const char* gl = Gbuf(cur) + lane_off;
-        const char* il = Ibuf(cur) + lane_off;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {  // K = 128 output positions: block row ks>>1, 16-position half ks&1
-            const int goff = ks * 16 * PITCH;
-            s16x8_t av[COT];
-#pragma unroll
-            for (int c = 0; c < COT; ++c) {
-                s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + c * G_PLANE + goff));
-                s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + c * G_PLANE + goff + 4 * PITCH));
-                av[c] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
-            const int prow = (ks >> 1) + row_shift;  // row inside the parity plane
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                // column parity odd for kx = 1; even columns start at lx (kx = 0) or lx + 1 (kx = 2)
-                const int pw = kx == 1 ? NO_C : NE_C;
-                const int pbase = odd_rows ? (kx == 1 ? P_OO : P_OE) : (kx == 1 ? P_EO : P_EE);
-                const int ioff = (pbase + prow * pw + (ks & 1) * 16 + (kx == 2 ? 1 : 0)) * PITCH;
-                s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(il + ioff));
-                s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(il + ioff + 4 * PITCH));
-                const s16x8_t bv = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                for (int c = 0; c < COT; ++c) acc[kx][c] = H16<T>::mma(av[c], bv, acc[kx][c]);
-            }
-        }
-    };
-
-    Regs R0;
-    if (pbeg < pend) {
-        gload(pbeg, R0);
-        lstore(0, R0);
-    }
-    __syncthreads();
-    const bool do_bias = p.bias_grad != nullptr && blockIdx.x == 0;
-    float bsum[EPS];
-#pragma unroll
-    for (int i = 0; i < EPS; ++i) bsum[i] = 0.f;
-    for (int patch = pbeg; patch < pend; ++patch) {
-        if (patch + 1 < pend) gload(patch + 1, R0);
-        compute(0);
-        if (do_bias) bias_grad_accumulate<T, COT, WP_THREADS>(Gbuf(0), tid, bsum);
-        __syncthreads();  // every wave is done reading this block
-        if (patch + 1 < pend) lstore(0, R0);
-        __syncthreads();
-    }
-    if (do_bias) bias_grad_flush<T, COT, WP_THREADS>(reinterpret_cast<float*>(lds), tid, bsum, p.bias_grad, co0, p.cout);
-    const int r = lane & 31, h = lane >> 5;
-    const int ci = ci0 + r;
-    if (ci < p.cin_total) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            float* dst = p.partial + (((int64_t)split * 9 + wave * 3 + kx) * w_rows) * p.cin_total;
-#pragma unroll
-            for (int c = 0; c < COT; ++c)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int co = co0 + 32 * c + (j & 3) + 8 * (j >> 2) + 4 * h;
-                    if (co < w_rows) dst[(int64_t)co * p.cin_total + ci] = acc[kx][c][j];
-                }
-        }
-    }
-}
-
-// First layer (Cin = 3) weight gradient, bf16 gout: dW[co][c][tap] = sum_p gout[p][co] * x[c][p + tap] straight from the PLANAR f32
-// image (variant 6) -- the generic kernels need an NHWC copy of the image padded to 32 channels (a 67 MB conversion per step
-// for 3 real channels).  GEMM view: D[co 32][k 32] += A[co][p] B[p][k], k = c*9 + tap (27 used): A fragments are the dense
-// kernel's transposed gout reads, B fragments eight consecutive image columns (f32 -> bf16) of the lane's (c, tap) row in
-// the LDS patch.  Four waves split the eight 16-position K steps of a 4x32 block; partial sums are reduced through LDS and
-// written as a standard [tap][co][cin_pad] slab (the batched reduce un-pads it).
-#define WC3_THREADS 256
-template <typename T>
-__global__ __launch_bounds__(WC3_THREADS) void wgrad3x3_c3_kernel(const falnet_wgrad_t p, int w_rows, int tiles_x, int tiles_y,
-                                                                  int patches_per_split) {
-    constexpr int PITCH = 64, SEGS = 4;
-    constexpr int G_BYTES = WP_TH * WP_TW * PITCH, X_FLOATS = 3 * (WP_TH + 2) * WP_PW;
-    constexpr int G_LOADS = WP_TH * WP_TW * SEGS, G_SLOTS = (G_LOADS + WC3_THREADS - 1) / WC3_THREADS;
-    constexpr int X_SLOTS = (X_FLOATS + WC3_THREADS - 1) / WC3_THREADS;
-    constexpr int BUF_BYTES = G_BYTES + ((X_FLOATS * 4 + 15) / 16) * 16;
-    __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES > 4 * 32 * 33 * 4 ? 2 * BUF_BYTES : 4 * 32 * 33 * 4];
-    auto Gbuf = [&](int b) -> char* { return lds + b * BUF_BYTES; };
-    auto Xbuf = [&](int b) -> float* { return reinterpret_cast<float*>(lds + b * BUF_BYTES + G_BYTES); };
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int split = blockIdx.z;
-    const float* x = reinterpret_cast<const float*>(p.src[0].ptr);
-    const int64_t HW = (int64_t)p.IH * p.IW;
-    const int npatch = p.B * tiles_x * tiles_y;
-    const int pbeg = split * patches_per_split, pend = min(pbeg + patches_per_split, npatch);
-
-    struct Regs { uint4 g[G_SLOTS]; float xv[X_SLOTS]; };
-    auto gload = [&](int patch, Regs& R) {
-        int q = patch;
-        const int tix = q % tiles_x;
-        q /= tiles_x;
-        const int tiy = q % tiles_y;
-        const int b = q / tiles_y;
-        const int y0 = tiy * WP_TH, x0 = tix * WP_TW;
-        const T* gbase = reinterpret_cast<const T*>(p.gout) + ((int64_t)b * p.TH * p.TW) * p.gC;
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WC3_THREADS;
-            const int seg = idx % SEGS, pix = idx / SEGS;
-            const int y = y0 + pix / WP_TW, xx = x0 + pix % WP_TW;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < G_LOADS && y < p.TH && xx < p.TW) v = *reinterpret_cast<const uint4*>(gbase + ((int64_t)y * p.TW + xx) * p.gC + seg * 8);
-            R.g[u] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < X_SLOTS; ++u) {
-            const int idx = tid + u * WC3_THREADS;
-            const int c = idx / ((WP_TH + 2) * WP_PW), rem = idx % ((WP_TH + 2) * WP_PW);
-            const int vy = y0 - 1 + rem / WP_PW, vx = x0 - 1 + rem % WP_PW;
-            R.xv[u] = (idx < X_FLOATS && vy >= 0 && vy < p.IH && vx >= 0 && vx < p.IW) ? x[((int64_t)b * 3 + c) * HW + (int64_t)vy * p.IW + vx] : 0.f;
-        }
-    };
-    auto lstore = [&](int buf, const Regs& R) {
-#pragma unroll
-        for (int u = 0; u < G_SLOTS; ++u) {
-            const int idx = tid + u * WC3_THREADS;
-            if (idx < G_LOADS) *reinterpret_cast<uint4*>(Gbuf(buf) + idx * 16) = R.g[u];
-        }
-#pragma unroll
-        for (int u = 0; u < X_SLOTS; ++u) {
-            const int idx = tid + u * WC3_THREADS;
-            if (idx < X_FLOATS) Xbuf(buf)[idx] = R.xv[u];
-        }
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    const int i16 = lane & 15, g16 = lane >> 4;
-    const int kh = g16 >> 1, cb = g16 & 1, q4 = i16 >> 2, pc = i16 & 3;
-    typedef s16x4 __attribute__((address_space(3))) * lds_v4;
-    const int lane_off = (kh * 8 + q4) * PITCH + (cb * 16 + pc * 4) * 2;
-    const int r = lane & 31, h = lane >> 5;
-    const bool kvalid = r < 27;
-    const int kc = r / 9, kt = r % 9;
-    const int koff = (kc * (WP_TH + 2) + kt / 3) * WP_PW + kt % 3;  // patch offset of this lane's (channel, tap)
-
-    const bool do_bias = p.bias_grad != nullptr;
-    float bsum[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) bsum[i] = 0.f;
-    Regs R0;
-    if (pbeg < pend) {
-        gload(pbeg, R0);
-        lstore(0, R0);
-    }
-    __syncthreads();
-    for (int patch = pbeg; patch < pend; ++patch) {
-        const int cur = (patch - pbeg) & 1;
-        if (patch + 1 < pend) gload(patch + 1, R0);
-        const char* gl = Gbuf(cur) + lane_off;
-        const float* X = Xbuf(cur);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int ks = wave * 2 + kk;  // 16-position K step: block row ks>>1, half ks&1
-            s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + ks * 16 * PITCH));
-            s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(gl + ks * 16 * PITCH + 4 * PITCH));
-            const s16x8_t av = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-            s16x8_t bv;
-            const float* xr = X + koff + (ks >> 1) * WP_PW + (ks & 1) * 16 + h * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bv[j] = (short)H16<T>::bits(kvalid ? xr[j] : 0.f);
-            acc = H16<T>::mma(av, bv, acc);
-        }
-        if (do_bias) bias_grad_accumulate<T, 1, WC3_THREADS>(Gbuf(cur), tid, bsum);
-        if (patch + 1 < pend) lstore(cur ^ 1, R0);
-        __syncthreads();
-    }
-    if (do_bias) {
-        bias_grad_flush<T, 1, WC3_THREADS>(reinterpret_cast<float*>(lds), tid, bsum, p.bias_grad, 0, p.cout);
-        __syncthreads();
-    }
-    // sum the four waves' partial tiles through LDS ([wave][co][k], pitch 33), then one thread per (co, k)
-    float* red = reinterpret_cast<float*>(lds);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int co = (j & 3) + 8 * (j >> 2) + 4 * h;
-        red[(wave * 32 + co) * 33 + r] = acc[j];
-    }
-    __syncthreads();
-    for (int e = tid; e < 32 * 27; e += WC3_THREADS) {
-        const int co = e / 27, k = e % 27;
-        const float v = red[(0 * 32 + co) * 33 + k] + red[(1 * 32 + co) * 33 + k] + red[(2 * 32 + co) * 33 + k] + red[(3 * 32 + co) * 33 + k];
-        const int c = k / 9, t = k % 9;
-        if (co < w_rows) p.partial[(((int64_t)split * 9 + t) * w_rows + co) * p.cin_total + c] = v;
-    }
-}
-
-// partial [nsplit][ntaps][w_rows][cin_total] -> OIHW f32, un-padding the (possibly two-group) channel axis
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int nsplit, int ntaps,
-                                                           int w_rows, int cin_total, float* __restrict__ grad, int cout,
-                                                           int cin, int c0_real, int c0_pad, int use_atomics) {
-    // block = (output channel co, 64 packed input channels); blockIdx.z = slab group.  Reads are coalesced along
-    // the packed channel axis; the [tap][ci] -> [ci][tap] transposition goes through LDS so that the OIHW
-    // writes are contiguous runs of ntaps*64 floats.
-    __shared__ float tile[64 * 9];
-    const int co = blockIdx.x, cp0 = blockIdx.y * 64;
-    const int ngroups = gridDim.z, grp = blockIdx.z;
-    const int s0 = (int)((int64_t)nsplit * grp / ngroups), s1 = (int)((int64_t)nsplit * (grp + 1) / ngroups);
-    const int64_t slab = (int64_t)ntaps * w_rows * cin_total;
-    for (int e = threadIdx.x; e < ntaps * 64; e += blockDim.x) {
-        const int t = e / 64, cl = e % 64;
-        float s = 0.f;
-        if (cp0 + cl < cin_total) {
-            const float* src = partial + ((int64_t)t * w_rows + co) * cin_total + cp0 + cl;
-            for (int k = s0; k < s1; ++k) s += src[k * slab];
-        }
-        tile[cl * ntaps + t] = s;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < ntaps * 64; e += blockDim.x) {
-        const int cl = e / ntaps, t = e % ntaps;
-        const int cp = cp0 + cl;
-        int ci = -1;
-        if (cp < c0_pad) {
-            if (cp < c0_real) ci = cp;
-        } else if (c0_real + (cp - c0_pad) < cin) {
-            ci = c0_real + (cp - c0_pad);
-        }
-        if (ci >= 0) {
-            float* dst = grad + ((int64_t)co * cin + ci) * ntaps + t;
-            if (use_atomics) atomicAdd(dst, tile[e]);
-            else *dst = tile[e];
-        }
-    }
-}
-
-// db[c] += sum_p g[p, c]: every thread owns one 8-channel segment (16-B bf16 / 32-B f32 loads) and strides over
-// pixels; rows of threads are summed through LDS, one atomic per channel per block.
-template <typename T>
-__global__ __launch_bounds__(256) void bias_grad_kernel(const T* __restrict__ g, int64_t npix, int gC, int cout,
-                                                        float* __restrict__ db) {
-    __shared__ float red[256 * 8];
-    const int segs = gC / 8;                       // gC is a multiple of 32
-    const int spb = segs < 256 ? segs : 256;       // segments handled per block pass
-    const int rows = 256 / spb;
-    const int sl = threadIdx.x % spb, rr = threadIdx.x / spb;
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int seg = blockIdx.y * spb + sl; seg < segs; seg += gridDim.y * spb) {
-        for (int64_t pix = (int64_t)blockIdx.x * rows + rr; pix < npix; pix += (int64_t)gridDim.x * rows) {
-            Vec8<T> v;
-            v.load(g + pix * gC + seg * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] += v.get(i);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) red[threadIdx.x * 8 + i] = acc[i];
-        __syncthreads();
-        if (rr == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                float t = 0.f;
-                for (int k = 0; k < rows; ++k) t += red[(k * spb + sl) * 8 + i];
-                if (seg * 8 + i < cout) atomicAdd(db + seg * 8 + i, t);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-    }
-}
-
-// entry lookup for the batched kernels: the block_begin column is fetched by n threads in parallel into LDS (a serial
-// walk of the global table cost ~0.5 us per entry per block)
-template <typename D>
-__device__ __forceinline__ int find_entry(const D* __restrict__ descs, int n, int* sh /* >= 64 ints */) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) sh[i] = descs[i].block_begin;
-    __syncthreads();
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)blockIdx.x >= sh[mid]) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// ---- batched forms: ONE launch reduces the split-K slabs of every layer / sums every bias gradient ----------
-// (a step has ~34 weight tensors and 13 biases; per-layer launches are launch-latency bound)
-// Slab reduce, streaming form.  A block owns `cob` consecutive output channels of one layer (cob * cin_total <= 1024 packed
-// input channels: for a fixed tap they are ONE contiguous run of the slab) and one group of slabs: thread i sums float4 i of
-// that run for all NT taps over the group's slabs -- every wave load is 1 KiB contiguous, NT (x2: two slabs per trip)
-// independent 16-B loads in flight per thread -- then the [tap][co][ci] sums are transposed through LDS ([co][ci][tap],
-// stride-NT stores: odd stride, conflict-free) and leave as contiguous runs of the OIHW gradient: plain STORES when the
-// block is the only writer (groups == 1 and the launch does not accumulate), 256-B-contiguous f32 atomics otherwise.
-// (The previous form gave every block ONE output channel and 64 input channels: 256-B runs per load, 64 x 9 scalar atomics
-// per block -- 3.5 TB/s on 758 MB of slabs.)
-template <int NT>
-__device__ __forceinline__ void wgrad_reduce_body(const falnet_reduce_t& d, int rel, float* __restrict__ tile /* 1024 * NT floats */, int accumulate) {
-    const int cob = d.cin_total >= 1024 ? 1 : 1024 / d.cin_total;
-    const int cblocks = (d.cout + cob - 1) / cob;
-    const int grp = rel % d.groups, cb = rel / d.groups;
-    if (cb >= cblocks) return;
-    const int co0 = cb * cob, nco = min(cob, d.cout - co0);
-    const int s0 = (int)((int64_t)d.nsplit * grp / d.groups), s1 = (int)((int64_t)d.nsplit * (grp + 1) / d.groups);
-    const int64_t tapstride = (int64_t)d.w_rows * d.cin_total, slab = (int64_t)NT * tapstride;
-    const int run = nco * d.cin_total;  // floats per tap of this block (a multiple of 32)
-    for (int base = 0; base < run; base += 1024) {  // (one trip unless cin_total > 1024)
-        const int i4 = base + threadIdx.x * 4;
-        float4 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i4 < run) {
-            const float* src = d.partial + (int64_t)co0 * d.cin_total + i4;
-            int k = s0;
-            for (; k + 2 <= s1; k += 2) {
-                float4 v[2][NT];
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) v[u][t] = *reinterpret_cast<const float4*>(src + (k + u) * slab + t * tapstride);
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        acc[t].x += v[u][t].x;
-                        acc[t].y += v[u][t].y;
-                        acc[t].z += v[u][t].z;
-                        acc[t].w += v[u][t].w;
-                    }
-            }
-            for (; k < s1; ++k) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const float4 v = *reinterpret_cast<const float4*>(src + k * slab + t * tapstride);
-                    acc[t].x += v.x;
-                    acc[t].y += v.y;
-                    acc[t].z += v.z;
-                    acc[t].w += v.w;
-                }
-            }
-            const int l = threadIdx.x * 4;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                tile[(l + 0) * NT + t] = acc[t].x;
-                tile[(l + 1) * NT + t] = acc[t].y;
-                tile[(l + 2) * NT + t] = acc[t].z;
-                tile[(l + 3) * NT + t] = acc[t].w;
-            }
-        }
-        __syncthreads();
-        const int nloc = min(1024, run - base);  // packed (co, ci) pairs of this trip
-        for (int e = threadIdx.x; e < nloc * NT; e += blockDim.x) {
-            const int l = e / NT, t = e - l * NT;
-            const int g = base + l;
-            const int col = g / d.cin_total, cp = g - col * d.cin_total;
-            int ci = -1;
-            if (cp < d.c0_pad) {
-                if (cp < d.c0_real) ci = cp;
-            } else if (d.c0_real + (cp - d.c0_pad) < d.cin) {
-                ci = d.c0_real + (cp - d.c0_pad);
-            }
-            if (ci >= 0) {
-                float* dst = d.grad + ((int64_t)(co0 + col) * d.cin + ci) * NT + t;
-                // no-return atomics pipeline; a read-modify-write would serialise one memory round trip per element
-                if (d.groups > 1 || accumulate) atomicAdd(dst, tile[e]);
-                else *dst = tile[e];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const falnet_reduce_t* __restrict__ descs, int n, int accumulate) {
-    __shared__ float tile[1024 * 9];
-    __shared__ int entry_begin[64];
-    const int li = find_entry(descs, n, entry_begin);
-    const falnet_reduce_t d = descs[li];
-    const int rel = blockIdx.x - d.block_begin;
-    if (d.ntaps == 9) wgrad_reduce_body<9>(d, rel, tile, accumulate);
-    else if (d.ntaps == 3) wgrad_reduce_body<3>(d, rel, tile, accumulate);
-    else if (d.ntaps == 1) wgrad_reduce_body<1>(d, rel, tile, accumulate);
-}
-
-// Deterministic form: `ws` != nullptr -> every block writes its per-channel sums to ws[blockIdx.x][512] (plain stores) and
-// bias_grad_finish_kernel adds them in block order (the atomic form's result depends on the order its blocks arrive in).
-__global__ __launch_bounds__(512) void bias_grad_finish_kernel(const falnet_biasgrad_t* __restrict__ descs, const float* __restrict__ ws) {
-    const falnet_biasgrad_t d = descs[blockIdx.x];
-    const int c = threadIdx.x;
-    if (c >= d.cout) return;
-    float s = 0.f;
-    for (int k = 0; k < d.blocks; ++k) s += ws[(int64_t)(d.block_begin + k) * 512 + c];
-    d.db[c] += s;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void bias_grad_batched_kernel(const falnet_biasgrad_t* __restrict__ descs, int n, float* __restrict__ ws = nullptr) {
-    __shared__ float red[256 * 8];
-    __shared__ int entry_begin[64];
-    const int li = find_entry(descs, n, entry_begin);
-    const falnet_biasgrad_t d = descs[li];
-    const int bx = blockIdx.x - d.block_begin, nbx = d.blocks;
-    const T* g = reinterpret_cast<const T*>(d.g);
-    const int segs = d.gC / 8;
-    const int spb = segs < 256 ? segs : 256;
-    const int rows = 256 / spb;
-    const int sl = threadIdx.x % spb, rr = threadIdx.x / spb;
-    for (int seg = sl; seg < segs; seg += spb) {
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int64_t pix = (int64_t)bx * rows + rr;
-        const int64_t stride = (int64_t)nbx * rows;
-        for (; pix + 7 * stride < d.npix; pix += 8 * stride) {  // eight independent 16-B loads in flight
-            Vec8<T> v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j].load(g + (pix + j * stride) * d.gC + seg * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                acc[i] += ((v[0].get(i) + v[1].get(i)) + (v[2].get(i) + v[3].get(i))) + ((v[4].get(i) + v[5].get(i)) + (v[6].get(i) + v[7].get(i)));
-        }
-        for (; pix < d.npix; pix += stride) {
-            Vec8<T> v;
-            v.load(g + pix * d.gC + seg * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] += v.get(i);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) red[threadIdx.x * 8 + i] = acc[i];
-        __syncthreads();
-        if (rr == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                float t = 0.f;
-                for (int k = 0; k < rows; ++k) t += red[(k * spb + sl) * 8 + i];
-                if (seg * 8 + i < d.cout) {
-                    if (ws) ws[(int64_t)blockIdx.x * 512 + seg * 8 + i] = t;
-                    else atomicAdd(d.db + seg * 8 + i, t);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// One block = one 32(cout) x 32(packed cin) tile of one layer, all taps, staged through LDS: the OIHW reads are
-// runs of taps*32 contiguous floats, the wf rows ([co][tap][32 cin]) and wd rows ([cin][tap][32 cout]) are written as
-// 32 contiguous elements.  (The element-per-thread version gathered with stride `taps` and scattered 2-byte writes.)
-// ADAM: the tile's master weights are UPDATED while they are loaded (torch.optim.Adam, Train_Stage1_K.py:177-180: the same arithmetic as
-// losses.hip: adam_dev_kernel) -- every real (co, ci, tap) element of a layer belongs to exactly one tile, so the optimiser step of all
-// packed layers and their re-pack are ONE pass over the masters (the stand-alone re-pack read the 68 MB Adam had just written again).
-struct PackAdam {
-    int64_t g_off, m_off, v_off;  // element offsets from a master weight to its gradient / first / second moment (the flat buffers share one layout)
-    float b1, b2, eps, grad_scale, step_size, rsqrt_bc2;
-};
-template <typename T, int TAPS, bool ADAM = false>
-__device__ __forceinline__ void pack_tile(const falnet_pack_t& d, int rel, float (&tile)[32][32 * 9 + 1], const PackAdam* ad = nullptr) {
-    const int ctiles = d.cin_pad / 32;
-    const int co0 = (rel / ctiles) * 32, cp0 = (rel % ctiles) * 32;
-    constexpr int rowlen = 32 * TAPS;
-    // packed columns cp0..cp0+31 map to a contiguous run of real channels (group boundaries are multiples of 32)
-    const int ci0 = cp0 < d.c0_pad ? cp0 : d.c0_real + (cp0 - d.c0_pad);
-    const int ci_end = cp0 < d.c0_pad ? d.c0_real : d.cin;   // exclusive bound of valid real channels for this tile
-    for (int e = threadIdx.x; e < 32 * rowlen; e += 256) {
-        const int r = e / rowlen, k = e % rowlen;            // r: cout row of the tile, k = cil*TAPS + t
-        const int co = co0 + r, ci = ci0 + k / TAPS;
-        float val = 0.f;
-        if (co < d.cout && ci < ci_end) {
-            float* wp = const_cast<float*>(d.w) + ((int64_t)co * d.cin + ci0) * TAPS + k;
-            val = *wp;
-            if constexpr (ADAM) {
-                const float gr = wp[ad->g_off] * ad->grad_scale;
-                const float m = ad->b1 * wp[ad->m_off] + (1.f - ad->b1) * gr;
-                const float v = ad->b2 * wp[ad->v_off] + (1.f - ad->b2) * gr * gr;
-                val -= ad->step_size * m / (sqrtf(v) * ad->rsqrt_bc2 + ad->eps);
-                *wp = val;
-                wp[ad->m_off] = m;
-                wp[ad->v_off] = v;
-            }
-        }
-        tile[r][k] = val;
-    }
-    __syncthreads();
-    T* wf = reinterpret_cast<T*>(d.wf);
-    T* wd = reinterpret_cast<T*>(d.wd);
-    // eight consecutive channels per thread and store (16 B in the 16-bit types): the first version stored one element per lane -- 2-B scalar
-    // stores, 128 B per wave instruction -- and ran the 204 MB of the step's re-pack at 2 TB/s
-    for (int e = threadIdx.x; e < 32 * TAPS * 4; e += 256) {
-        const int g = e & 3, t = (e >> 2) % TAPS, r = e / (4 * TAPS);
-        float vf[8], vd[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            vf[j] = tile[r][(8 * g + j) * TAPS + t];   // r = cout row, channels 8 g + j of the cin tile
-            vd[j] = tile[8 * g + j][r * TAPS + t];     // r = cin row, channels 8 g + j of the cout tile
-        }
-        T* pf = wf ? wf + ((int64_t)(co0 + r) * TAPS + t) * d.cin_pad + cp0 + 8 * g : nullptr;
-        T* pd = wd ? wd + ((int64_t)(cp0 + r) * TAPS + t) * d.cout_pad + co0 + 8 * g : nullptr;
-        if constexpr (sizeof(T) == 2) {
-            uint4 of, od;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                (&of.x)[k] = pack16x2<T>(vf[2 * k], vf[2 * k + 1]);
-                (&od.x)[k] = pack16x2<T>(vd[2 * k], vd[2 * k + 1]);
-            }
-            if (pf) *reinterpret_cast<uint4*>(pf) = of;
-            if (pd) *reinterpret_cast<uint4*>(pd) = od;
-        } else {
-            if (pf) {
-                reinterpret_cast<float4*>(pf)[0] = make_float4(vf[0], vf[1], vf[2], vf[3]);
-                reinterpret_cast<float4*>(pf)[1] = make_float4(vf[4], vf[5], vf[6], vf[7]);
-            }
-            if (pd) {
-                reinterpret_cast<float4*>(pd)[0] = make_float4(vd[0], vd[1], vd[2], vd[3]);
-                reinterpret_cast<float4*>(pd)[1] = make_float4(vd[4], vd[5], vd[6], vd[7]);
-            }
-        }
-    }
-}
-
-// One block = one 32(cout) x 32(packed cin) tile of one layer, all taps, staged through LDS: the OIHW reads are
-// runs of taps*32 contiguous floats, the wf rows ([co][tap][32 cin]) and wd rows ([cin][tap][32 cout]) are written as
-// 32 contiguous elements.  taps is 9, 3 or 1 (compile-time divisions).
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weights_batched_kernel(const falnet_pack_t* __restrict__ descs, int n) {
-    __shared__ float tile[32][32 * 9 + 1];
-    __shared__ int entry_begin[64];
-    const int li = find_entry(descs, n, entry_begin);
-    const falnet_pack_t d = descs[li];
-    const int rel = blockIdx.x - d.block_begin;
-    if (d.taps == 9) pack_tile<T, 9>(d, rel, tile);
-    else if (d.taps == 3) pack_tile<T, 3>(d, rel, tile);  // 3x1 / 1x3 (FAL_netA.py:73-76)
-    else pack_tile<T, 1>(d, rel, tile);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void adam_pack_batched_kernel(const falnet_pack_t* __restrict__ descs, int n, int64_t g_off, int64_t m_off, int64_t v_off,
-                                                                const float* __restrict__ state, float b1, float b2, float eps, float grad_scale,
-                                                                const float* __restrict__ scaler) {
-    __shared__ float tile[32][32 * 9 + 1];
-    __shared__ int entry_begin[64];
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;  // non-finite gradient somewhere: the whole update is skipped, the packed copies stay valid (grid-uniform)
-        grad_scale /= scaler[0];
-    }
-    const float t = state[1] + 1.0f;
-    PackAdam ad;
-    ad.g_off = g_off, ad.m_off = m_off, ad.v_off = v_off;
-    ad.b1 = b1, ad.b2 = b2, ad.eps = eps, ad.grad_scale = grad_scale;
-    ad.step_size = state[0] / (1.0f - powf(b1, t));
-    ad.rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
-    const int li = find_entry(descs, n, entry_begin);
-    const falnet_pack_t d = descs[li];
-    const int rel = blockIdx.x - d.block_begin;
-    if (d.no_update) {  // derived weights (their factors were updated by falnet_adam_ranges and re-composed before this launch)
-        if (d.taps == 9) pack_tile<T, 9>(d, rel, tile);
-        else if (d.taps == 3) pack_tile<T, 3>(d, rel, tile);
-        else pack_tile<T, 1>(d, rel, tile);
-    } else if (d.taps == 9) pack_tile<T, 9, true>(d, rel, tile, &ad);
-    else if (d.taps == 3) pack_tile<T, 3, true>(d, rel, tile, &ad);
-    else pack_tile<T, 1, true>(d, rel, tile, &ad);
-}
-
-// Sub-pixel weights of the deconv layers (conv_dma.hip: conv3x3_up2_dma_kernel): wu[co][pair][ci], pair = 4 (2 py + px) + 2 a + b
-template <typename T>
-__global__ __launch_bounds__(256) void pack_up2_batched_kernel(const falnet_pack_up2_t* __restrict__ descs, int n) {
-    __shared__ int entry_begin[64];
-    const int li = find_entry(descs, n, entry_begin);
-    const falnet_pack_up2_t d = descs[li];
-    const int rel = blockIdx.x - d.block_begin;
-    const int ncb = d.cin_pad / 32;
-    const int co0 = (rel / ncb) * 32, ci0 = (rel % ncb) * 32;
-    T* wu = reinterpret_cast<T*>(d.wu);
-    // one (co, ci) weight per thread and pass: its nine taps are loaded once and feed all sixteen (class, tap) sums (the first version looped over
-    // the 16384 outputs of the block with up to four dependent loads each: 40 us per step for three layers)
-    for (int e = threadIdx.x; e < 32 * 32; e += blockDim.x) {
-        const int ci = ci0 + (e & 31), co = co0 + (e >> 5);
-        float w[9];
-        const bool real = co < d.cout && ci < d.cin;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) w[t] = real ? d.w[((int64_t)co * d.cin + ci) * 9 + t] : 0.f;
-#pragma unroll
-        for (int pair = 0; pair < 16; ++pair) {
-            const int cls = pair >> 2, a = (pair >> 1) & 1, b = pair & 1, py = cls >> 1, px = cls & 1;
-            // 3x3 taps that coincide on low-resolution neighbour a (rows) / b (columns) for output parity py / px
-            const int ky0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), ky1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
-            const int kx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), kx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
-            float v = 0.f;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-                    if (ky >= ky0 && ky <= ky1 && kx >= kx0 && kx <= kx1) v += w[ky * 3 + kx];
-            wu[((int64_t)co * 16 + pair) * d.cin_pad + ci] = from_f32<T>(v);
-        }
-        if (d.wdd) {
-            // data-gradient form on the low-resolution grid (conv_dma.hip: conv2x2_up2d_dma16_kernel): wdd[ci][2 du + dv][e 2 Cp + f Cp + co], the
-            // coefficient of upstream pixel (2 (i + du) - 1 + e, 2 (j + dv) - 1 + f) in input position (i, j): per axis t = 2 d + parity selects the
-            // 3x3 taps {2}, {1, 2}, {0, 1}, {0}
-            T* wdd = reinterpret_cast<T*>(d.wdd);
-#pragma unroll
-            for (int tap = 0; tap < 4; ++tap)
-#pragma unroll
-                for (int ef = 0; ef < 4; ++ef) {
-                    const int ty = 2 * (tap >> 1) + (ef >> 1), tx = 2 * (tap & 1) + (ef & 1);
-                    const int ky0 = ty == 0 ? 2 : (ty == 1 ? 1 : 0), ky1 = ty == 0 ? 2 : (ty == 1 ? 2 : (ty == 2 ? 1 : 0));
-                    const int kx0 = tx == 0 ? 2 : (tx == 1 ? 1 : 0), kx1 = tx == 0 ? 2 : (tx == 1 ? 2 : (tx == 2 ? 1 : 0));
-                    float v = 0.f;
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx)
-                            if (ky >= ky0 && ky <= ky1 && kx >= kx0 && kx <= kx1) v += w[ky * 3 + kx];
-                    wdd[((int64_t)ci * 4 + tap) * (4 * d.cout_pad) + ef * d.cout_pad + co] = from_f32<T>(v);
-                }
-        }
-    }
-}
-
-extern "C" int falnet_pack_up2_batched(const falnet_pack_up2_t* descs_dev, int n, int total_blocks, int dtype, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= 64 && total_blocks > 0, "pack_up2_batched: bad argument");
-    FALNET_CHECK_ARG(dtype == FALNET_BF16 || dtype == FALNET_F16, "pack_up2_batched: 16-bit operand types only");
-#define PACKU_L(T) hipLaunchKernelGGL(pack_up2_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n)
-    FALNET_DISPATCH_16(dtype, PACKU_L);
-#undef PACKU_L
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_pack_weights_batched(const falnet_pack_t* descs_dev, int n, int total_blocks, int dtype, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= 64 && total_blocks > 0, "pack_weights_batched: bad argument (taps must be 9, 3 or 1, n <= 64)");
-#define PACK_B(T) hipLaunchKernelGGL(pack_weights_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n)
-    FALNET_DISPATCH_DTYPE(dtype, PACK_B);
-#undef PACK_B
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_adam_pack_batched(const falnet_pack_t* descs_dev, int n, int total_blocks, int dtype, int64_t g_off, int64_t m_off, int64_t v_off,
-                                        const float* state, float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= 64 && total_blocks > 0 && state, "adam_pack_batched: bad argument (n <= 64)");
-    FALNET_CHECK_ARG(g_off != 0 && m_off != 0 && v_off != 0 && g_off != m_off && g_off != v_off && m_off != v_off,
-                     "adam_pack_batched: gradient / moment buffers must be distinct from the weights and from each other");
-#define APACK_B(T) hipLaunchKernelGGL(adam_pack_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, g_off, m_off, v_off, \
-                                      state, b1, b2, eps, grad_scale, scaler)
-    FALNET_DISPATCH_DTYPE(dtype, APACK_B);
-#undef APACK_B
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_wgrad_reduce_blocks(int cout, int cin_total, int groups) {
-    if (cout <= 0 || cin_total <= 0 || groups <= 0) return -1;
-    const int cob = cin_total >= 1024 ? 1 : 1024 / cin_total;
-    return (cout + cob - 1) / cob * groups;
-}
-
-extern "C" int falnet_wgrad_reduce_batched(const falnet_reduce_t* descs_dev, int n, int total_blocks, int accumulate, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0, "wgrad_reduce_batched: bad argument");
-    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, accumulate ? 1 : 0);
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_bias_grad_batched(const falnet_biasgrad_t* descs_dev, int n, int total_blocks, int dtype, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0, "bias_grad_batched: bad argument");
-    FALNET_CHECK_ARG(!falnet_deterministic(), "bias_grad_batched: f32 atomics -- use falnet_bias_grad_batched_det in deterministic mode");
-#define BIAS_B(T) hipLaunchKernelGGL(bias_grad_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, (float*)nullptr)
-    FALNET_DISPATCH_DTYPE(dtype, BIAS_B);
-#undef BIAS_B
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_bias_grad_batched_det(const falnet_biasgrad_t* descs_dev, int n, int total_blocks, int dtype, float* ws, int64_t ws_floats,
-                                            void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0 && ws, "bias_grad_batched_det: bad argument");
-    FALNET_CHECK_ARG(ws_floats >= (int64_t)total_blocks * 512, "bias_grad_batched_det: workspace of %lld floats needed (512 per block)", (long long)total_blocks * 512);
-#define BIAS_B(T) hipLaunchKernelGGL(bias_grad_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, ws)
-    FALNET_DISPATCH_DTYPE(dtype, BIAS_B);
-#undef BIAS_B
-    hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(n), dim3(512), 0, (hipStream_t)stream, descs_dev, (const float*)ws);
-    FALNET_RETURN_LAUNCH();
-}
-
-// OIHW f32 -> packed operands (see falnet_hip.h)
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int cout, int cin, int taps,
-                                                           int c0_real, int c0_pad, int cin_pad, int cout_pad,
-                                                           T* __restrict__ wf, T* __restrict__ wd) {
-    const int64_t total = (int64_t)cout_pad * taps * cin_pad;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int cp = (int)(i % cin_pad), t = (int)((i / cin_pad) % taps), co = (int)(i / ((int64_t)cin_pad * taps));
-        int ci = -1;
-        if (cp < c0_pad) {
-            if (cp < c0_real) ci = cp;
-        } else if (c0_real + (cp - c0_pad) < cin) {
-            ci = c0_real + (cp - c0_pad);
-        }
-        const float v = (co < cout && ci >= 0) ? w[((int64_t)co * cin + ci) * taps + t] : 0.f;
-        if (wf) wf[i] = from_f32<T>(v);
-        if (wd) wd[((int64_t)cp * taps + t) * cout_pad + co] = from_f32<T>(v);
-    }
-}
-
 // ------------------------------------------------------------------------------------------ C-ABI
-static int check_src(const falnet_src_t& s, int kc, const char* who) {
-    FALNET_CHECK_ARG(s.ptr && s.C > 0 && s.C % kc == 0, "%s: source channels %d must be a positive multiple of %d", who, s.C, kc);
-    FALNET_CHECK_ARG(s.H > 0 && s.W > 0, "%s: empty source", who);
-    FALNET_CHECK_ARG((((uintptr_t)s.ptr) & 15) == 0, "%s: source pointer must be 16-B aligned", who);
-    return 0;
-}
-
 template <typename T, bool SWAP>
 static void launch_conv(const falnet_conv_t& p, int bn, dim3 grid, hipStream_t st) {
     if (bn == 128)
@@ -2879,8 +1597,22 @@ static bool falnet_mfma16_enabled() {
 }
 
 // The dispatcher's decision for one launch; shared by falnet_conv2d and falnet_conv2d_kernel_name.
+enum class ConvFamily {
+    Gather,            // conv_igemm_kernel: any tap table / stride (variants 1, 11, 12)
+    Patch,             // conv3x3_patch_kernel (variants 2-9)
+    WeightStationary,  // conv3x3_ws_kernel / conv3x3_ws2_kernel (variants 10 / 16; kcb = chunks, adb = two-phase form)
+    Dma,               // conv_dma.hip: conv3x3_dma_kernel (variants 13, 17, 20)
+    S2fDma,            // conv_dma.hip: conv3x3_s2f_dma_kernel (variant 15)
+    Up2Dma,            // conv_dma.hip: conv3x3_up2_dma_kernel (variant 18)
+    Deep,              // conv_dma.hip: conv3x3_deep_kernel (variant 19)
+    Dma2,              // conv_dma.hip: conv3x3_dma2_kernel (variants 21, 22)
+    Dma16,             // conv_dma.hip: conv3x3_dma16_kernel (variants 23-25)
+    Up2d,              // conv_dma.hip: conv2x2_up2d_dma16_kernel (variant 26)
+    Wave32,            // conv_wave.hip: conv3x3_wave32_kernel (variant 27)
+    Wave64p,           // conv_wave.hip: conv3x3_wave64p_kernel (variant 29)
+};
 struct ConvChoice {
-    int patch;               // 1: conv3x3_patch_kernel, 0: conv_igemm_kernel, 2: conv3x3_ws_kernel (kcb = chunks)
+    ConvFamily family;
     int bn, kcb, tps, adb, th, nwaves, flip, swap;
 };
 
@@ -2947,7 +1679,14 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         variant = 1;
     }
     if (g_disable_patch) variant = 1;
-    FALNET_CHECK_ARG((variant >= 0 && variant <= 10) || variant == 13 || variant == 15 || variant == 16 || variant == 17 || variant == 18 || variant == 19 || variant == 20 || (variant >= 21 && variant <= 27) || variant == 29, "conv2d: unknown variant %d", variant);
+    switch (variant) {  // the accepted variants; what each one selects follows below
+        case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7: case 8: case 9: case 10:
+        case 13: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 29:
+            break;
+        default:
+            falnet_set_error("conv2d: unknown variant %d", variant);
+            return -1;
+    }
     if (variant == 19) {  // levels 5-6: K-sliced one-shot LDS-DMA kernel with the epilogue in the last slice (conv_dma.hip: conv3x3_deep_kernel)
         if (!falnet_conv_deep_applicable(p)) {
             falnet_set_error("conv2d: variant 19 needs a 16-bit nine-tap stride-1/2 launch on maps of at most 128 positions (128 %% (TH TW) == 0), dense NHWC output, "
@@ -2956,7 +1695,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = 0;
         c.swap = 0;
-        c.patch = 6;
+        c.family = ConvFamily::Deep;
         c.bn = 64; c.kcb = p.ksplit * 32 == p.cin_total ? 1 : 2; c.tps = 9; c.adb = 1; c.th = 0; c.nwaves = falnet_conv_deep_mtiles(p);
         return 0;
     }
@@ -2967,7 +1706,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = 0;
         c.swap = 0;
-        c.patch = 4;
+        c.family = ConvFamily::S2fDma;
         c.bn = 64; c.kcb = 32; c.tps = 9; c.adb = 1; c.th = 8; c.nwaves = 8;
         return 0;
     }
@@ -2978,7 +1717,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 11;
+        c.family = ConvFamily::Wave64p;
         c.bn = 16; c.kcb = 32; c.tps = 9; c.adb = 1; c.th = 1; c.nwaves = 8;
         return 0;
     }
@@ -2989,7 +1728,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 10;
+        c.family = ConvFamily::Wave32;
         c.bn = 32; c.kcb = 32; c.tps = 9; c.adb = 1; c.th = 1; c.nwaves = 8;
         return 0;
     }
@@ -3000,7 +1739,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = 0;
         c.swap = 0;
-        c.patch = 9;
+        c.family = ConvFamily::Up2d;
         c.bn = 64; c.kcb = 32; c.tps = 4; c.adb = 1; c.th = 16; c.nwaves = 8;
         return 0;
     }
@@ -3011,7 +1750,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = 0;
         c.swap = 0;
-        c.patch = 5;
+        c.family = ConvFamily::Up2Dma;
         c.bn = 32; c.kcb = 64; c.tps = 16; c.adb = 1; c.th = 16; c.nwaves = 8;
         return 0;
     }
@@ -3024,7 +1763,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 8;
+        c.family = ConvFamily::Dma16;
         c.bn = 64; c.kcb = 32; c.tps = 9; c.adb = 1; c.th = th; c.nwaves = th == 4 ? 4 : 8;
         return 0;
     }
@@ -3036,7 +1775,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 7;
+        c.family = ConvFamily::Dma2;
         c.bn = 64; c.kcb = 16; c.tps = 9; c.adb = 1; c.th = th; c.nwaves = th / 4;
         return 0;
     }
@@ -3049,7 +1788,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 3;
+        c.family = ConvFamily::Dma;
         c.bn = 64; c.kcb = 64; c.tps = 9; c.adb = 1; c.th = th; c.nwaves = th == 4 ? 4 : 8;
         return 0;
     }
@@ -3064,7 +1803,7 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         c.flip = flip;
         c.swap = 0;
-        c.patch = 2;
+        c.family = ConvFamily::WeightStationary;
         c.bn = (p.w_rows % 64 == 0 && p.Cout > 32) ? 64 : 32;
         c.kcb = ctot * esz / 64;  // chunks
         c.tps = 9; c.adb = variant == 16; c.th = (c.bn == 64 ? 8 : 16) >> c.adb; c.nwaves = 8;
@@ -3084,12 +1823,12 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
     const bool bn64 = p.w_rows % 64 == 0 && p.Cout > 32;
     c.flip = flip;
     c.swap = planar ? 1 : 0;
-    c.patch = variant >= 2;
-    if (p.pool_out && !c.patch) {
+    c.family = variant >= 2 ? ConvFamily::Patch : ConvFamily::Gather;
+    if (p.pool_out && c.family == ConvFamily::Gather) {
         falnet_set_error("conv2d: the fused max pool needs a halo-patch variant (dense 3x3 stride-1 launch)");
         return -2;
     }
-    if (!c.patch) {
+    if (c.family == ConvFamily::Gather) {
         c.bn = forced_bn ? forced_bn : (p.w_rows % 128 == 0 && p.Cout > 64) ? 128 : (bn64 ? 64 : 32);
         c.kcb = 64; c.tps = 1; c.adb = 0; c.th = 0; c.nwaves = 4;
         return 0;
@@ -3118,41 +1857,138 @@ static bool ws2_whole_lines(const falnet_conv_t& p) {
     return on && p.nsrc == 1 && (int64_t)p.src[0].C * (p.dtype == FALNET_F32 ? 4 : 2) == 128;
 }
 
+// ---- the kernel families: launch functions of the three in this file, then ONE table row per family -----------------------------------
+// (a launch function returns 0 once its kernels are issued; falnet_conv2d reports a launch-configuration error)
+static int launch_gather(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st) {
+    const bool planar = p.out_layout == FALNET_OUT_PLANAR_F32;
+    const int bn = c.bn;
+    const int64_t M = (int64_t)p.B * p.TH * p.TW;
+    int ksplit = p.ksplit > 1 ? p.ksplit : 1;
+    if (ksplit > 1) {
+        FALNET_CHECK_ARG(!planar && p.splitk_ws && p.Cout % 8 == 0, "conv2d: split-K needs an NHWC output and a workspace");
+        FALNET_CHECK_ARG(M * p.w_rows * 4 <= p.splitk_ws_bytes, "conv2d: split-K workspace too small (%lld needed)", (long long)(M * p.w_rows * 4));
+        // no memset: the workspace is zero on entry by contract (the epilogue kernel below re-zeroes what it consumes)
+    }
+    const dim3 grid((unsigned)((M + CONV_BM - 1) / CONV_BM), (unsigned)((p.Cout + bn - 1) / bn), (unsigned)ksplit);
+#define GATHER_L(T)                                          \
+    if (planar) launch_conv<T, true>(p, bn, grid, st);       \
+    else launch_conv<T, false>(p, bn, grid, st);
+    FALNET_DISPATCH_DTYPE(p.dtype, GATHER_L);
+#undef GATHER_L
+    if (ksplit > 1) {
+        const int64_t total = M * (p.w_rows / 8);
+        const unsigned eg = (unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
+#define SPLITK_E(T) hipLaunchKernelGGL(splitk_epilogue_kernel<T>, dim3(eg), dim3(256), 0, st, p)
+        FALNET_DISPATCH_DTYPE(p.dtype, SPLITK_E);
+#undef SPLITK_E
+    }
+    return 0;
+}
+
+static int launch_patch(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st) {
+    const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + c.th - 1) / c.th;
+    const dim3 grid((unsigned)(p.B * tiles_x * tiles_y), (unsigned)((p.Cout + c.bn - 1) / c.bn));
+    bool launched = false;
+#define TRY_PATCH(T, BN, KCB, TPS, ADB, TH, NW)                                                                              \
+    if (!launched && c.bn == BN && c.kcb == KCB && c.tps == TPS && c.adb == (ADB ? 1 : 0) && c.th == TH) {                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_patch_kernel<T, BN, KCB, TPS, ADB, TH, NW>), grid, dim3(NW * 64), 0, st, p, \
+                       tiles_x, tiles_y, c.flip);                                                                          \
+    launched = true;                                                                                                       \
+    }
+#define PATCH_TABLE(T)                                                                                   \
+    TRY_PATCH(T, 128, 128, 1, true, 8, 4) TRY_PATCH(T, 64, 128, 1, true, 8, 4) TRY_PATCH(T, 32, 128, 1, true, 8, 4)      \
+    TRY_PATCH(T, 128, 128, 1, false, 8, 4) TRY_PATCH(T, 64, 128, 1, false, 8, 4) TRY_PATCH(T, 32, 128, 1, false, 8, 4)   \
+    TRY_PATCH(T, 128, 64, 1, true, 8, 4) TRY_PATCH(T, 64, 64, 1, true, 8, 4) TRY_PATCH(T, 32, 64, 1, true, 8, 4)         \
+    TRY_PATCH(T, 64, 64, 9, false, 8, 4) TRY_PATCH(T, 32, 64, 9, false, 8, 4)                                             \
+    TRY_PATCH(T, 64, 64, 9, true, 8, 4) TRY_PATCH(T, 32, 64, 9, true, 8, 4)                                               \
+    TRY_PATCH(T, 128, 64, 1, true, 16, 8) TRY_PATCH(T, 64, 64, 1, true, 16, 8) TRY_PATCH(T, 32, 64, 1, true, 16, 8)      \
+    TRY_PATCH(T, 64, 64, 9, false, 16, 8) TRY_PATCH(T, 32, 64, 9, false, 16, 8)                                           \
+    TRY_PATCH(T, 64, 64, 1, true, 4, 4) TRY_PATCH(T, 32, 64, 1, true, 4, 4)                                               \
+    TRY_PATCH(T, 64, 64, 9, false, 4, 4) TRY_PATCH(T, 32, 64, 9, false, 4, 4)
+    FALNET_DISPATCH_DTYPE(p.dtype, PATCH_TABLE);
+#undef PATCH_TABLE
+#undef TRY_PATCH
+    FALNET_CHECK_ARG(launched, "conv2d: no instantiation for bn=%d kcb=%d tps=%d adb=%d th=%d", c.bn, c.kcb, c.tps, c.adb, c.th);
+    return 0;
+}
+
+static int launch_ws(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st) {
+    const int ws_th = c.th;
+    const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + ws_th - 1) / ws_th;
+    const int ny = (p.Cout + c.bn - 1) / c.bn, ntiles = p.B * tiles_x * tiles_y;
+    int gx = 256 / ny;  // one persistent workgroup per CU (146 KB of LDS each)
+    if (gx < 1) gx = 1;
+    if (gx > ntiles) gx = ntiles;
+    const dim3 grid((unsigned)gx, (unsigned)ny);
+    const bool m16 = falnet_mfma16_enabled();  // v_mfma_f32_16x16x32 form (16-bit types)
+    const bool ws2_full = ws2_whole_lines(p);
+#define LAUNCH_WS1(K, T, BN, NCH) do { if (m16 && sizeof(T) == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(K<T, BN, NCH, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); \
+                                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(K<T, BN, NCH, false>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); } while (0)
+#define LAUNCH_WS2(T, BN, NCH) do { if (NCH == 2 && ws2_full) { if (m16 && sizeof(T) == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_ws2_kernel<T, BN, 2, true, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); \
+                                     else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_ws2_kernel<T, BN, 2, false, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); } \
+                                 else LAUNCH_WS1(conv3x3_ws2_kernel, T, BN, NCH); } while (0)
+#define LAUNCH_WS(T, BN, NCH) do { if (c.adb) LAUNCH_WS2(T, BN, NCH); else LAUNCH_WS1(conv3x3_ws_kernel, T, BN, NCH); } while (0)
+#define WS_TABLE(T)                                                                                 \
+    if (c.bn == 64) { if (c.kcb == 2) LAUNCH_WS(T, 64, 2); else LAUNCH_WS(T, 64, 1); }              \
+    else { if (c.kcb == 2) LAUNCH_WS(T, 32, 2); else LAUNCH_WS(T, 32, 1); }
+    FALNET_DISPATCH_DTYPE(p.dtype, WS_TABLE);
+#undef WS_TABLE
+#undef LAUNCH_WS
+#undef LAUNCH_WS1
+#undef LAUNCH_WS2
+    return 0;
+}
+
+static int ws_symbol(char* buf, int len, const char* t, const falnet_conv_t& p, const ConvChoice& c) {
+    const int m16 = (int)(falnet_mfma16_enabled() && p.dtype != FALNET_F32);
+    if (c.adb) return snprintf(buf, len, "_Z18conv3x3_ws2_kernelI%sLi%dELi%dELb%dELb%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, m16, (int)(c.kcb == 2 && ws2_whole_lines(p)));
+    return snprintf(buf, len, "_Z17conv3x3_ws_kernelI%sLi%dELi%dELb%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, m16);
+}
+
+// One row per family: the symbol of the instantiation a choice selects (t = the mangled operand type) and the function that launches it.
+// falnet_conv2d_kernel_name and falnet_conv2d both go through this table, so the reported symbol cannot drift from the kernel launched;
+// a new family is one enum member, one branch of choose_conv_kernel and one row here.
+struct ConvFamilyRow {
+    ConvFamily family;
+    int (*symbol)(char* buf, int len, const char* t, const falnet_conv_t& p, const ConvChoice& c);
+    int (*launch)(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st);
+};
+#define SYMBOL(...) [](char* buf, int len, const char* t, const falnet_conv_t& p, const ConvChoice& c) { return snprintf(buf, len, __VA_ARGS__); }
+#define LAUNCH(...) [](const falnet_conv_t& p, const ConvChoice& c, hipStream_t st) { return __VA_ARGS__; }
+static const ConvFamilyRow conv_families[] = {
+    {ConvFamily::Gather, SYMBOL("_Z17conv_igemm_kernelI%sLi%dELb%dEEv13falnet_conv_t", t, c.bn, c.swap), launch_gather},
+    {ConvFamily::Patch, SYMBOL("_Z20conv3x3_patch_kernelI%sLi%dELi%dELi%dELb%dELi%dELi%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, c.tps, c.adb, c.th, c.nwaves), launch_patch},
+    {ConvFamily::WeightStationary, ws_symbol, launch_ws},
+    {ConvFamily::Dma, SYMBOL("_Z18conv3x3_dma_kernelI%sLi%dELi%dEEv13falnet_conv_tiiii", t, c.th, c.nwaves), LAUNCH(falnet_conv_dma_launch(p, c.flip, st, c.th))},
+    {ConvFamily::S2fDma, SYMBOL("_Z22conv3x3_s2f_dma_kernelI%sLi%dEEv13falnet_conv_tiii", t, c.bn), LAUNCH(falnet_conv_s2f_dma_launch(p, st))},
+    {ConvFamily::Up2Dma, SYMBOL("_Z22conv3x3_up2_dma_kernelI%sEv13falnet_conv_tiiiii", t), LAUNCH(falnet_conv_up2_dma_launch(p, st))},
+    {ConvFamily::Deep, SYMBOL("_Z19conv3x3_deep_kernelI%sLi%dELi%dEEv13falnet_conv_t18falnet_deep_geom_t", t, c.kcb, c.nwaves), LAUNCH(falnet_conv_deep_launch(p, st))},
+    {ConvFamily::Dma2, SYMBOL("_Z19conv3x3_dma2_kernelI%sLb%dELi%dEEv13falnet_conv_tiiiii", t, p.pool_out ? 1 : 0, c.nwaves), LAUNCH(falnet_conv_dma2_launch(p, c.flip, st, c.th))},
+    {ConvFamily::Dma16, SYMBOL("_Z20conv3x3_dma16_kernelI%sLb%dELi%dELi%dELb%dEEv13falnet_conv_tiiii", t, p.pool_out ? 1 : 0, c.th, c.nwaves, p.out_layout == FALNET_OUT_PLANAR_F32 ? 1 : 0),
+     LAUNCH(falnet_conv_dma16_launch(p, c.flip, st, c.th))},
+    {ConvFamily::Up2d, SYMBOL("_Z25conv2x2_up2d_dma16_kernelI%sEv13falnet_conv_tiii", t), LAUNCH(falnet_conv_up2d_launch(p, st))},
+    {ConvFamily::Wave32, SYMBOL("_Z21conv3x3_wave32_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave32_launch(p, c.flip, st))},
+    {ConvFamily::Wave64p, SYMBOL("_Z22conv3x3_wave64p_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave64p_launch(p, c.flip, st))},
+};
+#undef SYMBOL
+#undef LAUNCH
+
+static const ConvFamilyRow* conv_family_row(ConvFamily f) {
+    for (const ConvFamilyRow& r : conv_families)
+        if (r.family == f) return &r;
+    falnet_set_error("conv2d: kernel family %d has no table row", (int)f);
+    return nullptr;
+}
+
 // Symbol of the kernel falnet_conv2d will launch for this descriptor (the name rocprofv3 reports): lets a harness
 // group launches by the real instantiation.
 extern "C" int falnet_conv2d_kernel_name(const falnet_conv_t* pp, char* buf, int len) {
     FALNET_CHECK_ARG(pp && buf && len > 0, "conv2d_kernel_name: bad argument");
     ConvChoice c;
     if (int r = choose_conv_kernel(*pp, c)) return r;
-    const char* t = pp->dtype == FALNET_BF16 ? "DF16b" : pp->dtype == FALNET_F16 ? "DF16_" : "f";
-    if (c.patch == 11)
-        snprintf(buf, len, "_Z22conv3x3_wave64p_kernelI%sEv13falnet_conv_tiiii", t);
-    else if (c.patch == 10)
-        snprintf(buf, len, "_Z21conv3x3_wave32_kernelI%sEv13falnet_conv_tiiii", t);
-    else if (c.patch == 9)
-        snprintf(buf, len, "_Z25conv2x2_up2d_dma16_kernelI%sEv13falnet_conv_tiii", t);
-    else if (c.patch == 8)
-        snprintf(buf, len, "_Z20conv3x3_dma16_kernelI%sLb%dELi%dELi%dELb%dEEv13falnet_conv_tiiii", t, pp->pool_out ? 1 : 0, c.th, c.nwaves, pp->out_layout == FALNET_OUT_PLANAR_F32 ? 1 : 0);
-    else if (c.patch == 7)
-        snprintf(buf, len, "_Z19conv3x3_dma2_kernelI%sLb%dELi%dEEv13falnet_conv_tiiiii", t, pp->pool_out ? 1 : 0, c.nwaves);
-    else if (c.patch == 6)
-        snprintf(buf, len, "_Z19conv3x3_deep_kernelI%sLi%dELi%dEEv13falnet_conv_t18falnet_deep_geom_t", t, c.kcb, c.nwaves);
-    else if (c.patch == 5)
-        snprintf(buf, len, "_Z22conv3x3_up2_dma_kernelI%sEv13falnet_conv_tiiiii", t);
-    else if (c.patch == 4)
-        snprintf(buf, len, "_Z22conv3x3_s2f_dma_kernelI%sLi%dEEv13falnet_conv_tiii", t, c.bn);
-    else if (c.patch == 3)
-        snprintf(buf, len, "_Z18conv3x3_dma_kernelI%sLi%dELi%dEEv13falnet_conv_tiiii", t, c.th, c.nwaves);
-    else if (c.patch == 2)
-    {
-        const int m16 = (int)(falnet_mfma16_enabled() && pp->dtype != FALNET_F32);
-        if (c.adb) snprintf(buf, len, "_Z18conv3x3_ws2_kernelI%sLi%dELi%dELb%dELb%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, m16, (int)(c.kcb == 2 && ws2_whole_lines(*pp)));
-        else snprintf(buf, len, "_Z17conv3x3_ws_kernelI%sLi%dELi%dELb%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, m16);
-    }
-    else if (c.patch)
-        snprintf(buf, len, "_Z20conv3x3_patch_kernelI%sLi%dELi%dELi%dELb%dELi%dELi%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, c.tps, c.adb, c.th, c.nwaves);
-    else
-        snprintf(buf, len, "_Z17conv_igemm_kernelI%sLi%dELb%dEEv13falnet_conv_t", t, c.bn, c.swap);
+    const ConvFamilyRow* row = conv_family_row(c.family);
+    if (!row) return -1;
+    row->symbol(buf, len, pp->dtype == FALNET_BF16 ? "DF16b" : pp->dtype == FALNET_F16 ? "DF16_" : "f", *pp, c);
     return 0;
 }
 
@@ -3185,88 +2021,9 @@ extern "C" int falnet_conv2d(const falnet_conv_t* pp, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     ConvChoice c;
     if (int r = choose_conv_kernel(p, c)) return r;
-    if (c.patch == 11) return falnet_conv_wave64p_launch(p, c.flip, st);
-    if (c.patch == 10) return falnet_conv_wave32_launch(p, c.flip, st);
-    if (c.patch == 9) return falnet_conv_up2d_launch(p, st);
-    if (c.patch == 8) return falnet_conv_dma16_launch(p, c.flip, st, c.th);
-    if (c.patch == 7) return falnet_conv_dma2_launch(p, c.flip, st, c.th);
-    if (c.patch == 6) return falnet_conv_deep_launch(p, st);
-    if (c.patch == 5) return falnet_conv_up2_dma_launch(p, st);
-    if (c.patch == 4) return falnet_conv_s2f_dma_launch(p, st);
-    if (c.patch == 3) return falnet_conv_dma_launch(p, c.flip, st, c.th);
-    if (c.patch == 2) {
-        const int ws_th = c.th;
-        const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + ws_th - 1) / ws_th;
-        const int ny = (p.Cout + c.bn - 1) / c.bn, ntiles = p.B * tiles_x * tiles_y;
-        int gx = 256 / ny;  // one persistent workgroup per CU (146 KB of LDS each)
-        if (gx < 1) gx = 1;
-        if (gx > ntiles) gx = ntiles;
-        const dim3 grid((unsigned)gx, (unsigned)ny);
-        const bool m16 = falnet_mfma16_enabled();  // v_mfma_f32_16x16x32 form (16-bit types)
-        const bool ws2_full = ws2_whole_lines(p);
-#define LAUNCH_WS1(K, T, BN, NCH) do { if (m16 && sizeof(T) == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(K<T, BN, NCH, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); \
-                                       else hipLaunchKernelGGL(HIP_KERNEL_NAME(K<T, BN, NCH, false>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); } while (0)
-#define LAUNCH_WS2(T, BN, NCH) do { if (NCH == 2 && ws2_full) { if (m16 && sizeof(T) == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_ws2_kernel<T, BN, 2, true, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); \
-                                         else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_ws2_kernel<T, BN, 2, false, true>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, c.flip); } \
-                                     else LAUNCH_WS1(conv3x3_ws2_kernel, T, BN, NCH); } while (0)
-#define LAUNCH_WS(T, BN, NCH) do { if (c.adb) LAUNCH_WS2(T, BN, NCH); else LAUNCH_WS1(conv3x3_ws_kernel, T, BN, NCH); } while (0)
-#define WS_TABLE(T)                                                                                 \
-    if (c.bn == 64) { if (c.kcb == 2) LAUNCH_WS(T, 64, 2); else LAUNCH_WS(T, 64, 1); }              \
-    else { if (c.kcb == 2) LAUNCH_WS(T, 32, 2); else LAUNCH_WS(T, 32, 1); }
-        FALNET_DISPATCH_DTYPE(p.dtype, WS_TABLE);
-#undef WS_TABLE
-#undef LAUNCH_WS
-#undef LAUNCH_WS1
-#undef LAUNCH_WS2
-        FALNET_RETURN_LAUNCH();
-    }
-    if (c.patch) {
-        const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + c.th - 1) / c.th;
-        const dim3 grid((unsigned)(p.B * tiles_x * tiles_y), (unsigned)((p.Cout + c.bn - 1) / c.bn));
-        bool launched = false;
-#define TRY_PATCH(T, BN, KCB, TPS, ADB, TH, NW)                                                                              \
-    if (!launched && c.bn == BN && c.kcb == KCB && c.tps == TPS && c.adb == (ADB ? 1 : 0) && c.th == TH) {                     \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_patch_kernel<T, BN, KCB, TPS, ADB, TH, NW>), grid, dim3(NW * 64), 0, st, p, \
-                           tiles_x, tiles_y, c.flip);                                                                          \
-        launched = true;                                                                                                       \
-    }
-#define PATCH_TABLE(T)                                                                                   \
-    TRY_PATCH(T, 128, 128, 1, true, 8, 4) TRY_PATCH(T, 64, 128, 1, true, 8, 4) TRY_PATCH(T, 32, 128, 1, true, 8, 4)      \
-    TRY_PATCH(T, 128, 128, 1, false, 8, 4) TRY_PATCH(T, 64, 128, 1, false, 8, 4) TRY_PATCH(T, 32, 128, 1, false, 8, 4)   \
-    TRY_PATCH(T, 128, 64, 1, true, 8, 4) TRY_PATCH(T, 64, 64, 1, true, 8, 4) TRY_PATCH(T, 32, 64, 1, true, 8, 4)         \
-    TRY_PATCH(T, 64, 64, 9, false, 8, 4) TRY_PATCH(T, 32, 64, 9, false, 8, 4)                                             \
-    TRY_PATCH(T, 64, 64, 9, true, 8, 4) TRY_PATCH(T, 32, 64, 9, true, 8, 4)                                               \
-    TRY_PATCH(T, 128, 64, 1, true, 16, 8) TRY_PATCH(T, 64, 64, 1, true, 16, 8) TRY_PATCH(T, 32, 64, 1, true, 16, 8)      \
-    TRY_PATCH(T, 64, 64, 9, false, 16, 8) TRY_PATCH(T, 32, 64, 9, false, 16, 8)                                           \
-    TRY_PATCH(T, 64, 64, 1, true, 4, 4) TRY_PATCH(T, 32, 64, 1, true, 4, 4)                                               \
-    TRY_PATCH(T, 64, 64, 9, false, 4, 4) TRY_PATCH(T, 32, 64, 9, false, 4, 4)
-        FALNET_DISPATCH_DTYPE(p.dtype, PATCH_TABLE);
-#undef PATCH_TABLE
-#undef TRY_PATCH
-        FALNET_CHECK_ARG(launched, "conv2d: no instantiation for bn=%d kcb=%d tps=%d adb=%d th=%d", c.bn, c.kcb, c.tps, c.adb, c.th);
-        FALNET_RETURN_LAUNCH();
-    }
-    const int bn = c.bn;
-    const int64_t M = (int64_t)p.B * p.TH * p.TW;
-    int ksplit = p.ksplit > 1 ? p.ksplit : 1;
-    if (ksplit > 1) {
-        FALNET_CHECK_ARG(!planar && p.splitk_ws && p.Cout % 8 == 0, "conv2d: split-K needs an NHWC output and a workspace");
-        FALNET_CHECK_ARG(M * p.w_rows * 4 <= p.splitk_ws_bytes, "conv2d: split-K workspace too small (%lld needed)", (long long)(M * p.w_rows * 4));
-        // no memset: the workspace is zero on entry by contract (the epilogue kernel below re-zeroes what it consumes)
-    }
-    const dim3 grid((unsigned)((M + CONV_BM - 1) / CONV_BM), (unsigned)((p.Cout + bn - 1) / bn), (unsigned)ksplit);
-#define GATHER_L(T)                                          \
-    if (planar) launch_conv<T, true>(p, bn, grid, st);       \
-    else launch_conv<T, false>(p, bn, grid, st);
-    FALNET_DISPATCH_DTYPE(p.dtype, GATHER_L);
-#undef GATHER_L
-    if (ksplit > 1) {
-        const int64_t total = M * (p.w_rows / 8);
-        const unsigned eg = (unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-#define SPLITK_E(T) hipLaunchKernelGGL(splitk_epilogue_kernel<T>, dim3(eg), dim3(256), 0, st, p)
-        FALNET_DISPATCH_DTYPE(p.dtype, SPLITK_E);
-#undef SPLITK_E
-    }
+    const ConvFamilyRow* row = conv_family_row(c.family);
+    if (!row) return -1;
+    if (int r = row->launch(p, c, st)) return r;
     FALNET_RETURN_LAUNCH();
 }
 
@@ -3359,214 +2116,5 @@ extern "C" int falnet_conv2d_multi(const falnet_conv_t* descs, int n, void* stre
         FALNET_DISPATCH_DTYPE(descs[0].dtype, SPLITK_M);
 #undef SPLITK_M
     }
-    FALNET_RETURN_LAUNCH();
-}
-
-static inline int round32(int v) { return (v + 31) / 32 * 32; }
-
-extern "C" int64_t falnet_wgrad_workspace_bytes(const falnet_wgrad_t* p) {
-    if (!p) return -1;
-    return (int64_t)p->nsplit * p->ntaps * round32(p->gC) * p->cin_total * (int64_t)sizeof(float);
-}
-
-// kernel selection of falnet_wgrad -- ONE place, also behind falnet_wgrad_fuses_bias (the host must not re-derive it)
-enum WgradKernel { WGK_BAD = -1, WGK_TAP = 0, WGK_PATCH11, WGK_PATCH12, WGK_PATCH21, WGK_S2, WGK_C3, WGK_ROWS, WGK_ROWS_S2, WGK_WAVE };
-bool falnet_wgrad_rows_applicable(const falnet_wgrad_t& p);           // wgrad_rows.hip
-int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_rows_s2_applicable(const falnet_wgrad_t& p);        // wgrad_rows.hip: row-streaming form of the stride-2 weight gradient (variant 8)
-int falnet_wgrad_rows_s2_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_wave_applicable(const falnet_wgrad_t& p);           // wgrad_wave.hip: wave-streaming kernel for 32-channel inputs (variant 9)
-int falnet_wgrad_wave_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_c3wave_applicable(const falnet_wgrad_t& p);         // wgrad_wave.hip: the first layer's gradient in the wave-streaming form (variant 6, IW % 4 == 0)
-int falnet_wgrad_c3wave_launch(const falnet_wgrad_t& p, hipStream_t st);
-
-static bool canonical_taps9(const falnet_wgrad_t& p) {
-    if (p.ntaps != 9) return false;
-    for (int t = 0; t < 9; ++t)
-        if (p.tap_dy[t] != t / 3 - 1 || p.tap_dx[t] != t % 3 - 1) return false;
-    return true;
-}
-
-// returns the kernel; on WGK_BAD the error text is set
-static WgradKernel choose_wgrad_kernel(const falnet_wgrad_t& p) {
-    const int w_rows = round32(p.gC);
-    const bool h16 = p.dtype == FALNET_BF16 || p.dtype == FALNET_F16;
-    const bool canon = canonical_taps9(p);
-    if (p.up2 && p.variant != 7) { falnet_set_error("wgrad: up2 (a deconv layer's gradient on the low-resolution grid) is a mode of variant 7 only"); return WGK_BAD; }
-    if (p.variant == 6) {  // first layer: planar f32 3-channel source (src[0].ptr = [B][3][IH][IW] f32), 16-bit gout, Cout 32
-        const bool ok = h16 && canon && p.isy == 1 && p.isx == 1 && p.TH == p.IH && p.TW == p.IW && p.gC == 32 && w_rows == 32 && p.cin_total == 32 && p.nsrc == 1;
-        if (!ok) { falnet_set_error("wgrad: variant 6 is the Cin=3 / Cout=32 first layer in bf16 / f16 (dense 3x3, cin_total 32)"); return WGK_BAD; }
-        return WGK_C3;
-    }
-    if (p.variant == 5) {  // stride-2 3x3 (16-bit): parity-plane halo kernel
-        bool ok = h16 && canon && p.isy == 2 && p.isx == 2 && p.TW >= 16 && p.TH == (p.IH + 1) / 2 && p.TW == (p.IW + 1) / 2;
-        for (int s = 0; s < p.nsrc && ok; ++s) ok = p.src[s].C % 32 == 0 && ((p.src[s].H == p.IH && p.src[s].W == p.IW) || (p.src[s].sy == 0 && p.src[s].sx == 0));
-        if (!ok) { falnet_set_error("wgrad: variant 5 needs a 16-bit 3x3 stride-2 pad-1 launch with sources at the input size"); return WGK_BAD; }
-        return WGK_S2;
-    }
-    if (p.variant == 8) {
-        if (!falnet_wgrad_rows_s2_applicable(p)) { falnet_set_error("wgrad: variant 8 needs a 16-bit 3x3 stride-2 pad-1 launch with ONE source at the input size"); return WGK_BAD; }
-        return WGK_ROWS_S2;
-    }
-    if (p.variant == 9) {
-        if (!falnet_wgrad_wave_applicable(p)) { falnet_set_error("wgrad: variant 9 needs a 16-bit dense 3x3 stride-1 launch over ONE 32-channel NHWC source at the launch size, gC 32 or 64, TW >= 32"); return WGK_BAD; }
-        return WGK_WAVE;
-    }
-    if (p.variant == 7) {
-        if (!falnet_wgrad_rows_applicable(p)) { falnet_set_error("wgrad: variant 7 needs a 16-bit dense 3x3 stride-1 launch with sources at the launch size or half of it (up2: ONE source at the launch size, nsplit a multiple of 4)"); return WGK_BAD; }
-        return WGK_ROWS;
-    }
-    // dense 3x3 stride-1 -> halo-patch kernel (one slab per workgroup; nsplit = pixel-range splits)
-    const bool dense = canon && p.isy == 1 && p.isx == 1 && p.TH == p.IH && p.TW == p.IW && p.TW >= 16 && !g_disable_patch && p.variant != 1;
-    if (dense) {
-        if (p.variant == 3 || p.variant == 4) {  // 32 x 64 / 64 x 32 channels per workgroup (register staged, two workgroups per CU)
-            const bool co2 = p.variant == 3;
-            if (!(h16 && (co2 ? w_rows : p.cin_total) % 64 == 0)) { falnet_set_error("wgrad: variant %d needs 16-bit operands and a channel count that is a multiple of 64", p.variant); return WGK_BAD; }
-            return co2 ? WGK_PATCH12 : WGK_PATCH21;
-        }
-        return WGK_PATCH11;
-    }
-    return WGK_TAP;
-}
-
-static int check_wgrad_desc(const falnet_wgrad_t& p) {
-    FALNET_CHECK_ARG(p.dtype == FALNET_F32 || p.dtype == FALNET_BF16 || p.dtype == FALNET_F16, "wgrad: bad dtype %d", p.dtype);
-    FALNET_CHECK_ARG(p.nsrc == 1 || p.nsrc == 2, "wgrad: nsrc=%d", p.nsrc);
-    int ctot = 0;
-    if (p.variant != 6) {  // (variant 6 reads a planar f32 3-channel image: its own checks)
-        for (int s = 0; s < p.nsrc; ++s) {
-            if (int r = check_src(p.src[s], 32, "wgrad")) return r;
-            ctot += p.src[s].C;
-        }
-        FALNET_CHECK_ARG(ctot == p.cin_total, "wgrad: sources carry %d channels, cin_total=%d", ctot, p.cin_total);
-    } else {
-        FALNET_CHECK_ARG(p.src[0].ptr && p.src[0].C == 3, "wgrad: variant 6 needs a 3-channel planar f32 source");
-    }
-    FALNET_CHECK_ARG(p.gout && p.gC > 0 && p.gC % 32 == 0 && p.nsplit >= 1 && p.ntaps >= 1 && p.ntaps <= 9, "wgrad: bad argument");
-    FALNET_CHECK_ARG(p.B > 0 && p.TH > 0 && p.TW > 0, "wgrad: empty shape");
-    FALNET_CHECK_ARG(p.cout >= 0 && p.cout <= p.gC, "wgrad: cout=%d exceeds gC=%d", p.cout, p.gC);
-    return 0;
-}
-
-static bool wgrad_kernel_fuses_bias(WgradKernel k) {
-    if (falnet_deterministic()) return false;  // the fused form adds with f32 atomics from every workgroup
-    return k == WGK_PATCH11 || k == WGK_PATCH12 || k == WGK_PATCH21 || k == WGK_S2 || k == WGK_C3 || k == WGK_ROWS || k == WGK_ROWS_S2 || k == WGK_WAVE;
-}
-
-extern "C" int falnet_wgrad_fuses_bias(const falnet_wgrad_t* pp) {
-    if (!pp || check_wgrad_desc(*pp) != 0) return 0;
-    return wgrad_kernel_fuses_bias(choose_wgrad_kernel(*pp)) ? 1 : 0;
-}
-
-extern "C" int falnet_wgrad(const falnet_wgrad_t* pp, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(pp, "wgrad: null descriptor");
-    falnet_wgrad_t p = *pp;
-    if (int r = check_wgrad_desc(p)) return r;
-    FALNET_CHECK_ARG(p.partial, "wgrad: no workspace");
-    if (p.cout == 0) p.cout = p.gC;
-    const int w_rows = round32(p.gC);
-    const WgradKernel k = choose_wgrad_kernel(p);
-    if (k == WGK_BAD) return -1;
-    if (p.bias_grad && !wgrad_kernel_fuses_bias(k)) {
-        falnet_set_error("wgrad: bias_grad is set but the selected kernel (%d) cannot fuse it -- ask falnet_wgrad_fuses_bias first", (int)k);
-        return -3;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles_x = (p.TW + WP_TW - 1) / WP_TW, tiles_y = (p.TH + WP_TH - 1) / WP_TH;
-    const int npatch = p.B * tiles_x * tiles_y;
-    const int pps = (npatch + p.nsplit - 1) / p.nsplit;
-    switch (k) {
-    case WGK_ROWS:
-        return falnet_wgrad_rows_launch(p, st);
-    case WGK_ROWS_S2:
-        return falnet_wgrad_rows_s2_launch(p, st);
-    case WGK_WAVE:
-        return falnet_wgrad_wave_launch(p, st);
-    case WGK_C3:
-        if (falnet_wgrad_c3wave_applicable(p)) return falnet_wgrad_c3wave_launch(p, st);
-#define WG_C3(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_c3_kernel<T>), dim3(1, 1, p.nsplit), dim3(WC3_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_C3);
-        break;
-    case WGK_S2:
-#define WG_S2_2(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_s2_kernel<T, 2>), dim3(p.cin_total / 32, w_rows / 64, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-#define WG_S2_1(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_s2_kernel<T, 1>), dim3(p.cin_total / 32, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        if (w_rows % 64 == 0) FALNET_DISPATCH_16(p.dtype, WG_S2_2);
-        else FALNET_DISPATCH_16(p.dtype, WG_S2_1);
-        break;
-    case WGK_PATCH12:
-#define WG_P12(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 1, 2>), dim3(p.cin_total / 32, w_rows / 64, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_P12);
-        break;
-    case WGK_PATCH21:
-#define WG_P21(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 2, 1>), dim3(p.cin_total / 64, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_P21);
-        break;
-    case WGK_PATCH11:
-#define WG_P11(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 1, 1>), dim3(p.cin_total / 32, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_DTYPE(p.dtype, WG_P11);
-        break;
-    default: {
-        const dim3 grid((p.cin_total + WG_BN - 1) / WG_BN, (w_rows + WG_BM - 1) / WG_BM, p.ntaps * p.nsplit);
-#define WG_TAP(T) hipLaunchKernelGGL(wgrad_kernel<T>, grid, dim3(CONV_THREADS), 0, st, p, w_rows)
-        FALNET_DISPATCH_DTYPE(p.dtype, WG_TAP);
-    }
-    }
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_wgrad_reduce(const float* partial, int nsplit, int ntaps, int cout_pad, int cin_total, float* grad,
-                                   int cout, int cin, int c0_real, int c0_pad, int accumulate, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(partial && grad && nsplit >= 1 && ntaps >= 1 && ntaps <= 9 && cout > 0 && cin > 0 && cout <= cout_pad, "wgrad_reduce: bad argument");
-    FALNET_CHECK_ARG(c0_real <= cin && c0_real <= c0_pad && c0_pad + (cin - c0_real) <= cin_total, "wgrad_reduce: channel groups do not fit");
-    // slab groups: enough blocks to fill the chip when the weight tensor is small and the slab count large
-    const int blocks = cout * ((cin_total + 63) / 64);
-    int groups = 1;
-    if (nsplit >= 16 && blocks < 1024) groups = (1024 + blocks - 1) / blocks;
-    if (groups > nsplit / 8) groups = nsplit / 8 > 0 ? nsplit / 8 : 1;
-    if (falnet_deterministic()) groups = 1;  // one writer per gradient element: slabs summed in slab order
-    const int use_atomics = (groups > 1 || accumulate) ? 1 : 0;
-    if (groups > 1 && !accumulate) {
-        hipError_t e = hipMemsetAsync(grad, 0, sizeof(float) * (size_t)cout * cin * ntaps, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cout, (cin_total + 63) / 64, groups), dim3(256), 0, (hipStream_t)stream, partial,
-                       nsplit, ntaps, cout_pad, cin_total, grad, cout, cin, c0_real, c0_pad, use_atomics);
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_bias_grad(const void* g, int64_t npix, int gC, int cout, float* db, int accumulate, int dtype,
-                                void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(g && db && npix > 0 && cout > 0 && cout <= gC, "bias_grad: bad argument");
-    FALNET_CHECK_ARG(gC % 32 == 0 && gC <= 2048, "bias_grad: unsupported channel count %d", gC);
-    if (!accumulate) {
-        hipError_t e = hipMemsetAsync(db, 0, sizeof(float) * cout, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int segs = gC / 8, spb = segs < 256 ? segs : 256, rows = 256 / spb;
-    int64_t gx = (npix + rows * 16 - 1) / (rows * 16);
-    gx = gx < 1 ? 1 : (gx > 512 ? 512 : gx);
-    if (falnet_deterministic()) gx = 1;  // one block = one add per channel (slow; the batched _det form is the training path)
-    const dim3 grid((unsigned)gx, 1);
-#define BIAS_L(T) hipLaunchKernelGGL(bias_grad_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)g, npix, gC, cout, db)
-    FALNET_DISPATCH_DTYPE(dtype, BIAS_L);
-#undef BIAS_L
-    FALNET_RETURN_LAUNCH();
-}
-
-extern "C" int falnet_pack_weights(const float* w_oihw, int cout, int cin, int taps, int c0_real, int c0_pad,
-                                   int cin_pad_total, int cout_pad, void* wf, void* wd, int dtype, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(w_oihw && (wf || wd) && cout > 0 && cin > 0 && taps >= 1, "pack_weights: bad argument");
-    FALNET_CHECK_ARG(cout_pad >= cout && cout_pad % 32 == 0 && cin_pad_total % 32 == 0, "pack_weights: pads must be multiples of 32");
-    FALNET_CHECK_ARG(c0_real <= cin && c0_real <= c0_pad && c0_pad + (cin - c0_real) <= cin_pad_total, "pack_weights: channel groups do not fit");
-    const int64_t total = (int64_t)cout_pad * taps * cin_pad_total;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-#define PACK_L(T) hipLaunchKernelGGL(pack_weights_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, cout, cin, taps, \
-                                   c0_real, c0_pad, cin_pad_total, cout_pad, (T*)wf, (T*)wd)
-    FALNET_DISPATCH_DTYPE(dtype, PACK_L);
-#undef PACK_L
     FALNET_RETURN_LAUNCH();
 }

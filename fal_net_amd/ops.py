@@ -146,15 +146,6 @@ def _timed(tag, flops, nbytes, launch, name=""):
     return call
 
 
-def conv_kernel_tag(dtype, w_rows, Cout, planar, variant=1):
-    """Kernel family falnet_conv2d dispatches to (conv.hip: falnet_conv2d), for the bench's per-family totals."""
-    dn = {torch.bfloat16: 'bf16', torch.float16: 'f16'}.get(dtype, 'f32')
-    if variant >= 2:
-        return f"conv3x3_patch_kernel<{dn},{ {2: 'kcb128', 3: 'kcb64', 4: 'single-stage', 5: 'double-stage', 6: 'kcb64,M512', 7: 'single-stage,M512'}[variant]}>"
-    bn = 128 if (w_rows % 128 == 0 and Cout > 64) else (64 if (w_rows % 64 == 0 and Cout > 32) else 32)
-    return f"conv_igemm_kernel<{dn},{bn},{'planar' if planar else 'nhwc'}>"
-
-
 def pad_c(c):
     return (c + CPAD - 1) // CPAD * CPAD
 
@@ -452,9 +443,8 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
     def launch(_keep=keep):
         L.check(lib.falnet_conv2d(ref, L.stream_ptr()), name)
     buf = C.create_string_buffer(160)
-    tag = buf.value.decode() if lib.falnet_conv2d_kernel_name(ref, buf, 160) == 0 and buf.value else \
-        conv_kernel_tag(dtype, w_rows, Cout, out_layout == L.OUT_PLANAR_F32, d.variant)
-    tag = buf.value.decode() or tag
+    L.check(lib.falnet_conv2d_kernel_name(ref, buf, 160), name)  # (fails exactly when falnet_conv2d would: both ask choose_conv_kernel)
+    tag = buf.value.decode()
     call = _timed(tag, flops, 0, launch, f"{name} v{d.variant} k{d.ksplit}")
     call.desc, call.ref = d, ref
     return call
@@ -641,13 +631,13 @@ def _autotune_conv(lib, d, ref, M, w_rows, Cout, reps=3):
 
 
 def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_pad, max_slabs, target_wgs=1536, up2=False):
-    """(variant, nsplit, kernel symbol) of one weight-gradient launch -- the host-side mirror of conv.hip's kernel choice
+    """(variant, nsplit, kernel symbol) of one weight-gradient launch -- the host-side mirror of wgrad.hip's kernel choice
     (falnet_wgrad re-checks the variant and fails loudly; whether the bias gradient is fused is ASKED from the library,
     falnet_wgrad_fuses_bias, never re-derived here)."""
     M = B * TH * TW
     h16 = dtype in (torch.bfloat16, torch.float16)
     tn = TYPE_SYM[dtype]
-    dense = len(taps) == 9 and stride_in == 1 and TW >= 16  # halo-patch kernel (conv.hip: falnet_wgrad)
+    dense = len(taps) == 9 and stride_in == 1 and TW >= 16  # halo-patch kernel (wgrad.hip: falnet_wgrad)
     c3 = len(srcs) == 1 and srcs[0].C == 3  # planar f32 image source (ops.planar_src): first-layer kernel, variant 6
     npatch = B * ((TH + 3) // 4) * ((TW + 31) // 32)
     if c3:

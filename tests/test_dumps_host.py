@@ -179,3 +179,13 @@ def test_binding_declares_the_dump_entry_points():
     assert "dump.hip" in _build.SOURCES
     from fal_net_amd import ops
     assert "dump.hip" not in ops._TUNE_SOURCES and _lib.EXPECTED_VERSION == 600  # the packaged autotune cache stays valid
+
+
+def test_optimiser_packer_and_weight_gradients_are_outside_the_tuned_sources():
+    import os
+    from fal_net_amd import _build, ops
+    for name in ("pack.hip", "wgrad.hip"):  # built, and a change to them leaves the packaged autotune cache valid
+        assert name in _build.SOURCES and name not in ops._TUNE_SOURCES
+    assert ops._TUNE_SOURCES == ("conv.hip", "conv_dma.hip", "conv_wave.hip", "conv_epilogue.h", "common.h")
+    assert "adam_pack_wd.hip" not in _build.SOURCES and not os.path.exists(os.path.join(_build.CSRC, "adam_pack_wd.hip"))  # ONE pack_tile: pack.hip
+    assert all(os.path.isfile(os.path.join(_build.CSRC, s)) for s in _build.SOURCES)
