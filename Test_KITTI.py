@@ -6,7 +6,8 @@ Two modes:
     loop (Test_KITTI.py:103-117 file-list dataset at batch size 1, :163-208 forward + flip / multi-scale post-processing,
     :255-271 per-image KITTI depth errors and EPE, :277-280 `errors.txt`) over full-size frames of mixed sizes.  Frames are decoded
     by loader workers (Pillow) and normalised on the GPU; the network, `ms_pp` resampling and flips are HIP kernels; the metric
-    chain is host-side numpy exactly as in the reference (fal_net_amd.myUtils).
+    chain is host-side numpy exactly as in the reference (fal_net_amd.myUtils), or -- `--device-metrics` -- HIP kernels that leave every
+    frame's numbers in a device-resident table read once at the end (fal_net_amd/metrics.py).
   * `--synthetic`: seeded image of `--height x --width` (native KITTI 375x1242 by default), timing only -- no dataset on the box.
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
 (:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
@@ -92,6 +93,8 @@ parser.add_argument('--dump', type=_dump_kinds, default=[], metavar='KINDS',
 parser.add_argument('--ply-format', default='binary', choices=['binary', 'ascii'], help='point clouds: binary_little_endian records, or the reference\'s ASCII file')
 parser.add_argument('--device-percentile', action='store_true', help="ms_pp's 95th percentile from the exact device-side percentile kernel instead of the "
                     'copy to the host and np.percentile')
+parser.add_argument('--device-metrics', action='store_true', help='KITTI depth errors (with -median too) and EPE from the device-side metric kernels '
+                    '(fal_net_amd/metrics.py) into a table read once after the last frame, instead of two full-size copies and float64 numpy per frame')
 
 
 def checkpoint_path(a):
@@ -153,7 +156,8 @@ def main():
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
-                                 with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile)
+                                 with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
+                                 device_metrics=args.device_metrics)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))

@@ -62,6 +62,8 @@ parser.add_argument('--train_list', default=os.path.join('Datasets', 'kitti_eige
                     help="training pairs, one 'left right' pair of paths relative to <data>/<dataName0> per line (the reference opens this "
                          "file relative to the working directory, Datasets/Kitti.py:37)")
 parser.add_argument('--save-path', default=None)
+parser.add_argument('--device-metrics', action='store_true', help='validation: RMSE, EPE and the KITTI depth errors from the device-side metric kernels '
+                    '(fal_net_amd/metrics.py) into a table read once per epoch, instead of per-frame copies and float64 numpy on the host')
 
 
 def main(step='stage1_step'):
@@ -211,7 +213,7 @@ def main(step='stage1_step'):
         is_best = False
         if val_loader is not None and rank == 0:  # :190-207: validate, keep the best RMSE
             res = train.validate(m_model, val_loader, max_disp=args.max_disp, min_disp=args.min_disp, rel_baset=args.rel_baset,
-                                 sparse=args.sparse, print_freq=args.print_freq)
+                                 sparse=args.sparse, print_freq=args.print_freq, device_metrics=args.device_metrics)
             print(json.dumps({'epoch': epoch, 'val_rmse': res['rmse'], 'val_epe': res['epe'], 'kitti': res['kitti']}), flush=True)
             if best < 0:
                 best = res['rmse']

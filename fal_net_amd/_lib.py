@@ -179,8 +179,14 @@ SIGNATURES = {
     "falnet_feature_to_u8": [_P, _P, _L, _P],
     "falnet_local_norm": [_P, _F, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_point_cloud": [_P, _F, _F, _F, _F, _P, _D, _D, _P, _P, _I, _I, _I, _P],
+    "falnet_metrics_workspace_bytes": [],
+    "falnet_depth_median_scale": [_P, _P, _I, _I, _I, _D, _D, _P, _P, _P],
+    "falnet_depth_errors": [_P, _P, _I, _I, _I, _D, _P, _D, _D, _P, _P, _P],
+    "falnet_epe": [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
+    "falnet_view_errors": [_P, _P, _F, _F, _F, _I, _I, _I, _P, _P, _P],
 }
-_RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64}
+_RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
+             "falnet_metrics_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

@@ -60,14 +60,16 @@ def dump_frame(writer, i, pan_model, left, disp, min_disp, max_pix):
 
 
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
-             print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False):
+             print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
     datasets.StereoValDataset; gt is a disparity map (Kitti2015) or a depth map (Eigen split, listdataset_test.py:43-46 reads both
     as uint16 / 256).  Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}.
     writer: a dumps.FrameWriter -- every frame's outputs are also written to disk (:211-253), after the timed region and after the metrics;
-    where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp."""
+    where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp.
+    device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
+    metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1)."""
     import time
     from . import datasets as DS
     from . import myUtils as utils
@@ -76,6 +78,10 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     pan_model.eval()
     epes, kitti, batch_time = utils.AverageMeter(), utils.multiAverageMeter(utils.kitti_error_names), utils.AverageMeter()
     n = 0
+    table = None
+    if device_metrics and with_metrics:
+        from . import metrics as M
+        table = M.MetricTable(len(loader.dataset) if hasattr(loader, "dataset") else 1, dev)
     with torch.no_grad():
         for i, batch in enumerate(loader):
             for left_u8, right_u8, gt in batch:
@@ -93,17 +99,30 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                 batch_time.update(time.time() - t0, 1)
                 if gt is not None and with_metrics:  # `-eval False`: forward and timing only (:255)
                     target = gt.to(dev).view(1, 1, *gt.shape)
-                    t_np, p_np = target.squeeze(1).cpu().numpy(), disp.float().squeeze(1).cpu().numpy()
-                    if data_name == "Kitti2015":  # :265-271
-                        epes.update(float(realEPE(disp, target, sparse=True)), 1)
-                        gt_depth, pred_depth = utils.disps_to_depths_kitti2015(t_np, p_np)
-                    else:  # Eigen split: :258-263
-                        gt_depth, pred_depth = utils.disps_to_depths_kitti(t_np, p_np)
-                    kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
+                    if table is not None:
+                        row = table.row(table.n)
+                        if data_name == "Kitti2015":
+                            M.epe(disp, target, sparse=True, out=row)
+                        M.depth_errors(disp, target, "kitti2015" if data_name == "Kitti2015" else "eigen", use_median=use_median, out=row)
+                    else:
+                        t_np, p_np = target.squeeze(1).cpu().numpy(), disp.float().squeeze(1).cpu().numpy()
+                        if data_name == "Kitti2015":  # :265-271
+                            epes.update(float(realEPE(disp, target, sparse=True)), 1)
+                            gt_depth, pred_depth = utils.disps_to_depths_kitti2015(t_np, p_np)
+                        else:  # Eigen split: :258-263
+                            gt_depth, pred_depth = utils.disps_to_depths_kitti(t_np, p_np)
+                        kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
                 if writer is not None:
                     dump_frame(writer, n, pan_model, left, disp, mn, mx)
                 n += 1
             if log is not None and i % print_freq == 0:
-                log('Test: [{0}/{1}]\t Time {2}\t a1 {3:.4f}'.format(i, len(loader), batch_time, kitti.avg[4]))  # :273-275
+                a1 = kitti.avg[4] if table is None else table.running_mean("a1")
+                log('Test: [{0}/{1}]\t Time {2}\t a1 {3:.4f}'.format(i, len(loader), batch_time, a1))  # :273-275
+    if table is not None:  # the one read of the table: the meters are filled frame by frame, as the host path fills them
+        res = table.result()
+        for e in res["epe"]:
+            epes.update(float(e), 1)
+        for errs in res["depth"]:
+            kitti.update(errs, 1)
     return {"epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg])), "kitti_table": repr(kitti), "n": n,
             "sec_per_image": batch_time.avg}

@@ -1,5 +1,6 @@
 """The part of the reference's myUtils.py the hot path needs: checkpoint writer, meters, and the KITTI metric
-chain behind `abs_rel vs ref` (myUtils.py:10-13,59-110,177-277).  Host-side numpy, as in the reference.  Also the validation scalars
+chain behind `abs_rel vs ref` (myUtils.py:10-13,59-110,177-277) and its Make3D pair (:280-334).  Host-side numpy, as in the reference; the
+same numbers come from the device through fal_net_amd/metrics.py.  Also the validation scalars
 (get_mea / get_rmse / get_psnr, :123-172) and the point cloud (:339-394), whose vertices come from the kernel behind fal_net_amd/dumps.py."""
 import os
 import shutil
@@ -8,6 +9,7 @@ import numpy as np
 import torch
 
 kitti_error_names = ['abs_rel', 'sq_rel', 'rms', 'log_rms', 'a1', 'a2', 'a3']
+make_error_names = ['abs_rel', 'sq_rel', 'rms', 'log10', 'a1', 'a2', 'a3']
 width_to_focal = {1242: 721.5377, 1241: 718.856, 1224: 707.0493, 1238: 718.3351, 1226: 707.0912, 1280: 738.2355}
 width_to_baseline = {1242: 0.9982 * 0.54, 1241: 0.9848 * 0.54, 1224: 1.0144 * 0.54, 1238: 0.9847 * 0.54,
                      1226: 0.9765 * 0.54, 1280: 0.54}
@@ -148,3 +150,34 @@ def disps_to_depths_kitti(gt_disparities, pred_disparities):
         gt_depths.append(gt_mask * gt_disp)
         pred_depths.append(pred_depth)
     return gt_depths, pred_depths
+
+
+def disps_to_depths_make(gt_disparities, pred_disparities, min_d=1.0, max_d=70.0):
+    """myUtils.py:280-309 (Make3D: gt is a depth, kept where 0 < gt < max_d; approximate camera 721 * 0.22; median scaling always on; both
+    depths capped to [min_d, max_d]).  Returns the MASKED 1-d arrays."""
+    gt_depths, pred_depths = [], []
+    for gt_disp, pred_disp in zip(gt_disparities, pred_disparities):
+        gt_mask, pred_mask = (gt_disp > 0) * (gt_disp < max_d), pred_disp > 0
+        pred_depth = 721 * 0.22 / (pred_disp + (1.0 - pred_mask))
+        gt_depth, pred_depth = gt_disp[gt_mask], pred_depth[gt_mask]
+        pred_depth = np.median(gt_depth) / np.median(pred_depth) * pred_depth
+        pred_depth[pred_depth > max_d] = max_d
+        pred_depth[pred_depth < min_d] = min_d
+        gt_depth[gt_depth > max_d] = max_d
+        gt_depth[gt_depth < min_d] = min_d
+        gt_depths.append(gt_depth)
+        pred_depths.append(pred_depth)
+    return gt_depths, pred_depths
+
+
+def compute_make_errors(gt, pred):
+    """myUtils.py:312-334: as compute_kitti_errors without scaling and clamping, with mean |log10 gt - log10 pred| for log_rms (make_error_names)."""
+    mask = gt > 0
+    gt, pred = gt[mask], pred[mask]
+    thresh = np.maximum(gt / pred, pred / gt)
+    a1, a2, a3 = (thresh < 1.25).mean(), (thresh < 1.25 ** 2).mean(), (thresh < 1.25 ** 3).mean()
+    rmse = np.sqrt(((gt - pred) ** 2).mean())
+    log10 = np.abs(np.log10(gt) - np.log10(pred)).mean()
+    abs_rel = np.mean(np.abs(gt - pred) / gt)
+    sq_rel = np.mean(((gt - pred) ** 2) / gt)
+    return [abs_rel, sq_rel, rmse, log10, a1, a2, a3]

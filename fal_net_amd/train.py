@@ -606,11 +606,13 @@ class GraphedStage1Step:
         return self.out
 
 
-def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, sparse=True, print_freq=100, log=print):
+def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, sparse=True, print_freq=100, log=print, device_metrics=False):
     """Train_Stage1_K.py:279-347 / Train_Stage2_K.py validate(): full-size forward (disp + synthesised right view + masks), RMSE of
     the synthesised view, EPE and the KITTI depth errors against the ground-truth disparity.  `val_loader` yields lists of
     (left_u8, right_u8, disp) from fal_net_amd.datasets.StereoValDataset (batch size 1 in the reference, :152).
-    Returns {'rmse', 'epe', 'kitti': {name: value}} (the reference returns the RMSE, :345)."""
+    Returns {'rmse', 'epe', 'kitti': {name: value}} (the reference returns the RMSE, :345).
+    device_metrics: the three numbers of a frame come from the kernels behind fal_net_amd/metrics.py into a device-resident table that is read
+    after the last frame (and on the iterations that print): no per-frame copy of a map or a metric to the host."""
     import numpy as np
     from . import datasets as DS
     from . import myUtils as utils
@@ -619,6 +621,10 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
     was_training = model.training
     model.eval()
     rmses, epes, kitti = utils.AverageMeter(), utils.AverageMeter(), utils.multiAverageMeter(utils.kitti_error_names)
+    table = None
+    if device_metrics:
+        from . import metrics as M
+        table = M.MetricTable(len(val_loader.dataset) if hasattr(val_loader, "dataset") else 1, dev)
     with torch.no_grad():
         for i, batch in enumerate(val_loader):
             for left_u8, right_u8, disp_gt in batch:
@@ -626,6 +632,14 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
                 mx = torch.full((1, 1, 1), float(max_disp) * rel_baset, device=dev)
                 mn = mx * min_disp / max_disp
                 p_im, disp, maskL, maskRL = model(left, mn, mx, ret_disp=True, ret_pan=True, ret_subocc=True)
+                if table is not None:
+                    row = table.row(table.n)
+                    M.view_errors(p_im, right, out=row)
+                    if disp_gt is not None:
+                        target = disp_gt.to(dev).view(1, 1, *disp_gt.shape)
+                        M.epe(disp, target, sparse=sparse, out=row)
+                        M.depth_errors(disp, target, "kitti2015", out=row)
+                    continue
                 rmses.update(float(utils.get_rmse(p_im, right)))
                 if disp_gt is not None:
                     target = disp_gt.to(dev).view(1, 1, *disp_gt.shape)
@@ -633,7 +647,15 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
                     gt_depth, pred_depth = utils.disps_to_depths_kitti2015(target.squeeze(1).cpu().numpy(), disp.squeeze(1).cpu().numpy())
                     kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0]), 1)
             if log is not None and i % print_freq == 0:
-                log('Test: [{0}/{1}]\t RMSE {2:.3f}'.format(i, len(val_loader), rmses.avg))
+                log('Test: [{0}/{1}]\t RMSE {2:.3f}'.format(i, len(val_loader), rmses.avg if table is None else table.running_mean("rmse")))
+    if table is not None:  # the one read of the table: the meters are filled frame by frame, as the host path fills them
+        res = table.result()
+        for r in res["view"]:
+            rmses.update(float(r[0]))
+        for e in res["epe"]:
+            epes.update(float(e), 1)
+        for errs in res["depth"]:
+            kitti.update(errs, 1)
     model.train(was_training)
     return {"rmse": rmses.avg, "epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg]))}
 

@@ -554,6 +554,60 @@ int falnet_local_norm(const float* x, float mean_r, float mean_g, float mean_b, 
 int falnet_point_cloud(const float* img, float mean_r, float mean_g, float mean_b, float rgb_scale, const float* disp, double focal, double baseline,
                        float* out_planar, void* out_packed, int B, int H, int W, void* stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip; myUtils.py:123-172,196-334, loss_functions.py:124-173) ---------------------------------------
+ * The numbers an evaluation loop produces per frame, computed from the planar f32 maps where they lie and written into one ROW of a caller-owned,
+ * device-resident table of doubles (FALNET_MET_ROW doubles per frame; a call writes only the columns of its own group).  The host reads the table
+ * once after the last frame.  workspace: falnet_metrics_workspace_bytes() bytes, 8-byte aligned, owned by ONE stream at a time (calls on a stream
+ * may share it: they are ordered).  Every reduction is deterministic: a fixed grid writes per-workgroup partial sums, a finalising kernel adds them
+ * in index order; no floating-point atomics.  Two calls on the same inputs give bit-identical rows.  None of these is replayable. */
+#define FALNET_DEPTH_KITTI2015 0 /* disps_to_depths_kitti2015: gt is a disparity, both depths fb / (d + (1 - [d > 0])), masked by gt > 0, whole frame */
+#define FALNET_DEPTH_EIGEN 1     /* disps_to_depths_kitti: rows H-219:H-4, columns 44:1180, gt is a depth, masked by gt > 0 */
+#define FALNET_DEPTH_MAKE3D 2    /* disps_to_depths_make + compute_make_errors: gt is a depth, masked by 0 < gt < max_d, always median-scaled, log10 term */
+#define FALNET_MET_ROW 24
+#define FALNET_MET_ABS_REL 0 /* depth group: the seven metrics in the order of kitti_error_names / make_error_names ... */
+#define FALNET_MET_SQ_REL 1
+#define FALNET_MET_RMS 2
+#define FALNET_MET_LOG 3 /* log_rms; make3d: mean |log10 gt - log10 pred| */
+#define FALNET_MET_A1 4
+#define FALNET_MET_A2 5
+#define FALNET_MET_A3 6
+#define FALNET_MET_N 7    /* ... the number of pixels that count, the three threshold counts as integers ... */
+#define FALNET_MET_N_A1 8
+#define FALNET_MET_N_A2 9
+#define FALNET_MET_N_A3 10
+#define FALNET_MET_SCALE 11 /* ... and the median scale factor with the two medians it is made of (1, 0, 0 without median scaling) */
+#define FALNET_MET_MEDIAN_GT 12
+#define FALNET_MET_MEDIAN_PRED 13
+#define FALNET_MET_EPE 14 /* end-point group: the mean and the number of pixels it is over */
+#define FALNET_MET_EPE_N 15
+#define FALNET_MET_RMSE 16 /* view group: get_rmse, get_mea, get_psnr and the three sums and the count behind them */
+#define FALNET_MET_MEA 17
+#define FALNET_MET_PSNR 18
+#define FALNET_MET_VIEW_SUM_SQ 19
+#define FALNET_MET_VIEW_SUM_ABS 20
+#define FALNET_MET_VIEW_SUM_RSQ 21
+#define FALNET_MET_VIEW_N 22
+int64_t falnet_metrics_workspace_bytes(void);
+/* np.median(gt[mask]) / np.median(pred[mask]) of the depths of one frame (H x W f32 maps; `mode` and `fb` = focal * baseline as below), exact:
+ * a radix select over the f64 depths with a 64-bit key, the number of selected pixels and the ranks found on the device; an even count takes the
+ * mean of the two middle order statistics, in the type the host's array has (f32 for the ground truth of eigen / make3d).  scale_out: 4 doubles on
+ * the device -- {factor, median gt, median pred, n} -- that falnet_depth_errors takes as `scale` without a host read (NaN when nothing is selected). */
+int falnet_depth_median_scale(const float* pred_disp, const float* gt, int H, int W, int mode, double fb, double max_d, double* scale_out,
+                              void* workspace, void* stream);
+/* compute_kitti_errors / compute_make_errors of one frame: disparity -> depth per `mode`, optional scale (NULL: none; make3d requires it), both depths
+ * clamped to [min_d, max_d], then abs_rel, sq_rel, rms, log term and the three `max(gt / pred, pred / gt) < 1.25^k` rates, in f64 per pixel in the
+ * host's order.  fb: focal * 0.54 (kitti2015), focal * baseline (eigen), 721 * 0.22 (make3d), formed by the caller.  eigen needs H >= 219, W >= 1180.
+ * min_d and max_d must be f32 values (the host clamps an f32 ground truth in f32). */
+int falnet_depth_errors(const float* pred_disp, const float* gt, int H, int W, int mode, double fb, const double* scale, double min_d, double max_d,
+                        double* row, void* workspace, void* stream);
+/* realEPE: pred (B, 1, h, w) sampled bilinearly (align_corners=True, the arithmetic of falnet_resize_planar; equal sizes: the identity) at the size of
+ * target (B, 1, H, W); mean of |target - up| over target != 0 (sparse) or over every pixel, accumulated in f64 */
+int falnet_epe(const float* pred, int h, int w, const float* target, int B, int H, int W, int sparse, double* row, void* workspace, void* stream);
+/* get_rmse / get_mea / get_psnr of a synthesised view against the real one, both (B, 3, H, W) normalised by the RGB mean: out = clamp(255 (x + mean), 0,
+ * 255), lab = 255 (y + mean) in f32; sums of (out - lab)^2, |out - lab| and (round(out) - lab)^2 in f64 */
+int falnet_view_errors(const float* out, const float* label, float mean_r, float mean_g, float mean_b, int B, int H, int W, double* row, void* workspace,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
