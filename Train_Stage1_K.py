@@ -57,6 +57,12 @@ parser.add_argument('--synthetic', action='store_true', help='seeded random pair
 parser.add_argument('--gpu-augment', action='store_true',
                     help='synthetic mode: start from KITTI-sized uint8 "decoded" pairs and run the reference augmentation chain on '
                          'the GPU every step (fal_net_amd.data_transforms.StereoAugment) instead of cycling pre-made float batches')
+parser.add_argument('--batch-augment', action='store_true',
+                    help='augment a whole batch with ONE launch (fal_net_amd.data_transforms.BatchAugment: same draws and same values as the '
+                         'per-sample StereoAugment, coefficients computed on the device) on the loader path and on the synthetic --gpu-augment path')
+parser.add_argument('--resident-data', action='store_true',
+                    help='decode this rank\'s shard of the training list ONCE into an HBM arena (fal_net_amd.datasets.ResidentStereoPairs) and draw '
+                         'every batch from it: no training loader after the build; implies --batch-augment; validation is unchanged')
 parser.add_argument('--dtype', default='bf16', choices=['bf16', 'f16', 'f32'], help='compute dtype (f32 = exact-f32 MFMA parity path)')
 parser.add_argument('--train_list', default=os.path.join('Datasets', 'kitti_eigen_train.txt'),
                     help="training pairs, one 'left right' pair of paths relative to <data>/<dataName0> per line (the reference opens this "
@@ -122,7 +128,14 @@ def main(step='stage1_step'):
     def lr_at(epoch):  # MultiStepLR(milestones, gamma=0.5), fast-forwarded like Train_Stage1_K.py:181-184
         return args.lr * (0.5 ** sum(1 for m in args.milestones if epoch >= m))
 
-    train_loader = val_loader = None
+    train_loader = val_loader = resident = batch_augment = None
+    if args.resident_data:
+        args.batch_augment = True
+    if args.resident_data and args.synthetic:
+        raise SystemExit('--resident-data keeps a real training list in HBM: give -d/--data, not --synthetic')
+    if args.batch_augment:
+        from fal_net_amd import data_transforms as DT
+        batch_augment = DT.BatchAugment(args.crop_height, args.crop_width)  # the ranges of StereoAugment
     if not args.synthetic:
         if not args.data:
             raise SystemExit('give the dataset root with -d/--data (or run with --synthetic)')
@@ -132,8 +145,15 @@ def main(step='stage1_step'):
         pairs = DS.read_pair_list(args.train_list, root)
         if not pairs:
             raise SystemExit('no training pair of {} exists under {}'.format(args.train_list, root))
-        train_loader = DS.make_loader(DS.StereoPairDataset(root, pairs, max_pix=args.max_disp, fix=True), args.batch_size, args.workers,
-                                      shuffle=True, rank=rank, world=world)
+        if args.resident_data:
+            # every rank keeps its own strided shard (equal lengths: every rank runs the same number of steps) and permutes inside it
+            per_rank = len(pairs) // world
+            if per_rank < args.batch_size:
+                raise SystemExit('{} training pairs per rank are fewer than one batch of {}'.format(per_rank, args.batch_size))
+            resident = DS.ResidentStereoPairs(root, pairs[:per_rank * world][rank::world], dev, max_pix=args.max_disp, workers=args.workers)
+        else:
+            train_loader = DS.make_loader(DS.StereoPairDataset(root, pairs, max_pix=args.max_disp, fix=True), args.batch_size, args.workers,
+                                          shuffle=True, rank=rank, world=world)
         vroot = os.path.join(args.data, args.vdataName)
         vtriples = DS.kitti2015_pairs(vroot) if os.path.isdir(vroot) else []
         if vtriples and rank == 0:  # only rank 0 validates: the other ranks start no validation workers
@@ -141,8 +161,8 @@ def main(step='stage1_step'):
         real_augment = DT.StereoAugment(args.crop_height, args.crop_width)
         if rank == 0:
             print('=> {} training pairs, {} validation pairs'.format(len(pairs), len(vtriples)))
-    vtriples_any = train_loader is not None and bool(vtriples)  # the same on every rank (same files): gates the post-validation barrier
-    steps_per_epoch = args.epoch_size or (len(train_loader) if train_loader is not None else 100)
+    vtriples_any = not args.synthetic and bool(vtriples)  # the same on every rank (same files): gates the post-validation barrier
+    steps_per_epoch = args.epoch_size or (len(train_loader) if train_loader is not None else len(resident) // args.batch_size if resident is not None else 100)
     best = -1
     # synthetic mode: a small pool of seeded batches resident in HBM, cycled (generating 25 MB of noise on the CPU every
     # step would make the script loader-bound; a real loader prefetches asynchronously)
@@ -163,13 +183,20 @@ def main(step='stage1_step'):
         if augment is None:
             return pool[i % len(pool)]
         import torch as _t
-        views = [augment(raw[(i * args.batch_size + b) % len(raw)]) for b in range(args.batch_size)]
+        picked = [raw[(i * args.batch_size + b) % len(raw)] for b in range(args.batch_size)]
+        if batch_augment is not None:
+            return (*batch_augment(picked), mx_aug)
+        views = [augment(p) for p in picked]
         return _t.stack([v[0] for v in views]), _t.stack([v[1] for v in views]), mx_aug
     def real_batches():
         """Decoded uint8 pairs -> GPU -> augmented (B, 3, ch, cw) tensors; the upload of the next list overlaps the current step
         (pinned memory, non_blocking)."""
         import torch as _t
         for batch in train_loader:
+            if batch_augment is not None:
+                v0, v1 = batch_augment([[l.to(dev, non_blocking=True), r.to(dev, non_blocking=True)] for l, r, _ in batch])
+                yield v0, v1, _t.tensor([abs(x) for _, _, x in batch], device=dev).view(-1, 1, 1)
+                continue
             views = [real_augment([l.to(dev, non_blocking=True), r.to(dev, non_blocking=True)]) for l, r, _ in batch]
             mxs = _t.tensor([abs(x) for _, _, x in batch], device=dev).view(-1, 1, 1)
             yield _t.stack([v[0] for v in views]), _t.stack([v[1] for v in views]), mxs
@@ -182,6 +209,8 @@ def main(step='stage1_step'):
         if train_loader is not None and getattr(train_loader, 'sampler', None) is not None and hasattr(train_loader.sampler, 'set_epoch'):
             train_loader.sampler.set_epoch(epoch)
         stream = real_batches() if train_loader is not None else None
+        if resident is not None:  # a fresh permutation of the resident shard per epoch, seeded by (rank, epoch)
+            stream = (resident.batch(idx, batch_augment) for idx in resident.epoch_batches(epoch, args.batch_size, seed=rank))
         for i in range(steps_per_epoch):
             if stream is not None:
                 try:

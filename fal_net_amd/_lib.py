@@ -93,6 +93,12 @@ class BiasGradDesc(C.Structure):
                 ("blocks", C.c_int32), ("block_begin", C.c_int32)]
 
 
+class Aug(C.Structure):  # falnet_aug_t: one sample of falnet_augment_batch
+    _fields_ = [("src", C.c_uint64 * 2), ("H", C.c_int32), ("W", C.c_int32), ("rw", C.c_int32), ("rh", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("flip", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("bright", C.c_double),
+                ("cb", (C.c_double * 3) * 2)]
+
+
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 # name -> argtypes (restype int unless listed in _RESTYPES); mirrors include/falnet_hip.h one to one
 SIGNATURES = {
@@ -159,6 +165,7 @@ SIGNATURES = {
     "falnet_hflip": [_P, _P, _L, _I, _P],
     "falnet_resample_u8": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "falnet_augment_normalize": [_P, _I, _I, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _F, _F, _F, _P, _P],
+    "falnet_augment_batch": [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P],
     "falnet_rowmax": [_P, _P, _I, _L, _P],
     "falnet_gemm_f32_small": [_P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _P],
     "falnet_resize_planar": [_P, _P, _L, _I, _I, _I, _I, _I, _F, _P],

@@ -6,6 +6,8 @@ launches (falnet_resample_u8 x2 per image, falnet_augment_normalize x1 per image
 left/right flip-swap, gamma / brightness / per-channel brightness, ArrayToTensor and both Normalize steps, producing the planar
 f32 tensors the model consumes.  The random draws are made on the host IN THE REFERENCE'S ORDER from the same generators
 (`np.random` for the scale factor, Python `random` for the rest), so a seeded run reproduces the reference's augmentation.
+BatchAugment is the same chain for a whole batch in ONE launch (falnet_augment_batch): same draws, same values, the resampling
+coefficients computed on the device and only the crop window resampled.
 
 No CPU fallback: the tensors must live on the GPU.
 """
@@ -135,3 +137,106 @@ class StereoAugment:
                                                  MEAN[0], MEAN[1], MEAN[2], L.ptr(out), L.stream_ptr()), "augment_normalize")
             outs.append(out)
         return outs
+
+
+# ---- the whole batch in one launch (csrc/augment_batch.hip) ---------------------------------------------------------------------------
+AUG_DTYPE = np.dtype(L.Aug)  # falnet_aug_t as a structured dtype: the record table is filled through a numpy view of pinned memory
+MAX_SCALE = 2                # FALNET_AUG_MAX_SCALE: resized / source within [1 / 2, 2] per axis
+
+
+def pack_records(sources, params, table=None):
+    """falnet_aug_t records of a batch.  `sources`: per sample (address_left, address_right, H, W) of the uint8 (H, W, 3) frames;
+    `params`: per sample a dict in draw_params's format.  RandomHorizontalFlip swaps the views as well as mirroring them
+    (data_transforms.py:98-100), so src[j] is the frame that FEEDS output position j, and the per-image factors of RandomCBrightness
+    are drawn for the positions after the swap: cb[j] = cbright[j].  Needs no GPU."""
+    n = len(sources)
+    if len(params) != n:
+        raise ValueError(f"{n} samples but {len(params)} parameter sets")
+    rec = np.zeros(n, AUG_DTYPE) if table is None else table[:n]
+    for i, ((left, right, h, w), prm) in enumerate(zip(sources, params)):
+        flip = bool(prm["flip"])
+        cb = prm["cbright"] if prm["cbright"] is not None else ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+        rec[i] = ((right, left) if flip else (left, right), h, w, prm["rw"], prm["rh"], prm["x1"], prm["y1"], int(flip), 0,
+                  float(prm["gamma"] or 0.0), float(prm["bright"] or 0.0), cb)
+    return rec
+
+
+class _Slot:
+    """One in-flight record table: pinned host memory, its device copy, and the event after the launch that reads it."""
+
+    def __init__(self, n, device):
+        self.n = n
+        self.host = torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        self.table = self.host.numpy().view(AUG_DTYPE)
+        self.dev = torch.empty(n * AUG_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self.event = None
+
+
+class BatchAugment:
+    """StereoAugment for a whole batch: one record-table upload and ONE C call (falnet_augment_batch) per batch.
+
+    __call__(pairs) with `pairs` a list of [left_u8, right_u8] (H, W, 3) uint8 CUDA tensors (sizes may differ from sample to sample)
+    returns (view0, view1), planar f32 (B, 3, crop_h, crop_w), equal to torch.stack over a loop of StereoAugment: the random draws
+    are made once per sample in sample order, so a seeded run draws exactly what that loop draws.  The resampling coefficients are
+    computed on the device; only the crop window is resampled.  Runs on the current torch stream."""
+
+    SLOTS = 4  # record tables in flight: a slot is reused only after the launch that read it has finished
+
+    def __init__(self, crop_height, crop_width, down=0.75, up=1.5, gamma=(0.8, 1.2), brightness=(0.5, 2.0), cbrightness=(0.8, 1.2)):
+        self.size, self.down, self.up = (int(crop_height), int(crop_width)), down, up
+        self.gamma, self.brightness, self.cbrightness = gamma, brightness, cbrightness
+        self._slots, self._next = {}, 0
+
+    def draw(self, h, w):
+        return draw_params(h, w, self.size[0], self.size[1], self.down, self.up, self.gamma, self.brightness, self.cbrightness)
+
+    def __call__(self, pairs, params=None, out=None):
+        sources = []
+        for left, right in pairs:
+            for t in (left, right):
+                if not (t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous()):
+                    raise RuntimeError("BatchAugment needs contiguous uint8 (H, W, 3) tensors")
+            if left.shape != right.shape:
+                raise RuntimeError(f"the views of a pair differ in size: {tuple(left.shape)} and {tuple(right.shape)}")
+            sources.append((left.data_ptr(), right.data_ptr(), left.shape[0], left.shape[1]))
+        device = next((t.device for p in pairs for t in p if t.is_cuda), None)
+        return self.run(sources, params, device, out)
+
+    def run(self, sources, params=None, device=None, out=None):
+        """The same for frames given as (address_left, address_right, H, W): separately allocated tensors and the frames of a
+        resident arena (datasets.ResidentStereoPairs) go through the same call."""
+        th, tw = self.size
+        n = len(sources)
+        if n == 0:
+            raise ValueError("empty batch")
+        if params is None:
+            params = [self.draw(h, w) for _, _, h, w in sources]
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if out is None:
+            out = (torch.empty(n, 3, th, tw, dtype=torch.float32, device=device), torch.empty(n, 3, th, tw, dtype=torch.float32, device=device))
+        for o in out:
+            if not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (n, 3, th, tw)):
+                raise RuntimeError(f"out: two contiguous f32 CUDA tensors of shape {(n, 3, th, tw)}")
+        slots = self._slots.setdefault(str(device), [])
+        k = self._next % self.SLOTS
+        self._next += 1
+        if len(slots) <= k:
+            slots.append(_Slot(max(n, 16), device))
+        if slots[k].n < n:
+            if slots[k].event is not None:
+                slots[k].event.synchronize()
+            slots[k] = _Slot(n, device)
+        slot = slots[k]
+        if slot.event is not None:
+            slot.event.synchronize()  # (long finished unless more than SLOTS batches are queued ahead of the device)
+        pack_records(sources, params, slot.table)
+        nbytes = n * AUG_DTYPE.itemsize
+        stream = torch.cuda.current_stream(device)
+        with torch.cuda.device(device):
+            slot.dev[:nbytes].copy_(slot.host[:nbytes], non_blocking=True)
+            L.check(L.lib().falnet_augment_batch(L.ptr(slot.dev), slot.host.data_ptr(), n, th, tw, MEAN[0], MEAN[1], MEAN[2], L.ptr(out[0]), L.ptr(out[1]),
+                                                 stream.cuda_stream), "augment_batch")
+            if slot.event is None:
+                slot.event = torch.cuda.Event()
+            slot.event.record(stream)
+        return out[0], out[1]

@@ -130,3 +130,85 @@ def to_model_input(img_u8, device):
     Kitti2015.py:88-90): uint8 (H, W, 3) -> planar f32 (1, 3, H, W) on `device`."""
     x = img_u8.to(device, non_blocking=True).permute(2, 0, 1).float().div_(255.0)
     return (x - torch.tensor(MEAN, device=device).view(3, 1, 1)).unsqueeze(0).contiguous()
+
+
+# ---- the training set decoded once and kept in HBM -------------------------------------------------------------------------------------
+def epoch_batches(n, epoch, batch_size, rank=0, world=1, seed=0):
+    """Index lists of one epoch over `n` samples: a torch.randperm seeded by (seed, epoch), the same on every rank, sharded like
+    DistributedSampler with drop_last (disjoint strided shards of equal length), then cut into full batches.  Needs no GPU."""
+    g = torch.Generator()
+    g.manual_seed(int(seed) + int(epoch))
+    perm = torch.randperm(n, generator=g).tolist()
+    per_rank = n // world
+    mine = perm[:per_rank * world][rank::world]
+    for k in range(0, per_rank - per_rank % batch_size, batch_size):
+        yield mine[k:k + batch_size]
+
+
+def _frame_size(path):
+    from PIL import Image
+    with Image.open(path) as im:  # reads the header only
+        return im.size[1], im.size[0]
+
+
+class ResidentStereoPairs:
+    """Every pair of a list decoded ONCE (by the loader workers of make_loader, fix=True order: left, right) into one uint8 arena on the
+    device; batches are then augmented straight from the arena (BatchAugment.run on arena addresses), with no decode, no loader and no
+    host-to-device image traffic after the build.  The Eigen split is 22 600 pairs x 2 x 375 x 1242 x 3 B = 63 GB of an MI355X's 288 GB.
+
+    frames[2 * i + view] = (offset, H, W) of view `view` of pair i in `arena`.  The arena is refused -- nothing is loaded partially --
+    when it would take more than `max_fraction` of the device memory that is free."""
+
+    ALIGN = 256
+
+    def __init__(self, root, pairs, device, max_pix=300, workers=4, max_fraction=0.6):
+        self.device, self.max_pix = torch.device(device), float(max_pix)
+        pairs = list(pairs)
+        sizes, offset = [], 0
+        for lp, rp in pairs:
+            for p in (lp, rp):
+                h, w = _frame_size(os.path.join(root, p))
+                sizes.append((offset, h, w))
+                offset += -(-(h * w * 3) // self.ALIGN) * self.ALIGN
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if offset > max_fraction * free:
+            raise MemoryError(f"the resident training set needs {offset} bytes, more than {max_fraction:.0%} of the {free} bytes free on {self.device}: "
+                              "train from the loader instead (without --resident-data) or shard the list over more devices")
+        self.frames = torch.tensor(sizes, dtype=torch.int64).view(-1, 3)
+        self.arena = torch.empty(max(offset, 1), dtype=torch.uint8, device=self.device)
+        loader = make_loader(StereoPairDataset(root, pairs, max_pix=max_pix, fix=True), batch_size=8, workers=workers, shuffle=False, drop_last=False)
+        i = 0
+        for batch in loader:
+            for left, right, _ in batch:
+                for view, img in enumerate((left, right)):
+                    off, h, w = sizes[2 * i + view]
+                    if tuple(img.shape) != (h, w, 3):
+                        raise RuntimeError(f"{pairs[i][view]} decodes to {tuple(img.shape)}, its header says {(h, w, 3)}")
+                    self.arena[off:off + h * w * 3].copy_(img.reshape(-1), non_blocking=True)
+                i += 1
+        del loader
+        torch.cuda.synchronize(self.device)
+        self._base = self.arena.data_ptr()
+        self._sizes = sizes
+
+    def __len__(self):
+        return len(self._sizes) // 2
+
+    def frame(self, index, view):
+        """View `view` of pair `index` as a (H, W, 3) uint8 tensor that aliases the arena."""
+        off, h, w = self._sizes[2 * index + view]
+        return self.arena[off:off + h * w * 3].view(h, w, 3)
+
+    def epoch_batches(self, epoch, batch_size, rank=0, world=1, seed=0):
+        return epoch_batches(len(self), epoch, batch_size, rank, world, seed)
+
+    def batch(self, indices, augment, params=None, out=None):
+        """(left, right, max_pix) of the pairs `indices`, augmented by `augment` (a data_transforms.BatchAugment)."""
+        sources = []
+        for i in indices:
+            (ol, h, w), (orr, h2, w2) = self._sizes[2 * i], self._sizes[2 * i + 1]
+            if (h, w) != (h2, w2):
+                raise RuntimeError(f"the views of pair {i} differ in size: {(h, w)} and {(h2, w2)}")
+            sources.append((self._base + ol, self._base + orr, h, w))
+        left, right = augment.run(sources, params, self.device, out)
+        return left, right, torch.full((len(sources), 1, 1), self.max_pix, device=self.device)

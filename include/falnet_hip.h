@@ -489,6 +489,26 @@ int falnet_augment_normalize(const uint8_t* src, int H, int W, int x1, int y1, i
                              double bright, double cb0, double cb1, double cb2, float mean0, float mean1, float mean2,
                              float* dst, void* stream);
 
+/* The whole chain above for a BATCH in one launch (csrc/augment_batch.hip): per sample, both views -- bicubic resize of the uint8
+ * [H][W][3] frame to rw x rh restricted to the crop window [y1,y1+th) x [x1,x1+tw) (Pillow's two-pass order and rounding, so bit-exact
+ * with falnet_resample_u8 x2 + crop), optional mirror, the colour chain and both Normalize steps of falnet_augment_normalize -> planar f32
+ * out0 / out1 [B][3][th][tw].  The resampling coefficients are computed on the device in f64, in the order of
+ * fal_net_amd.data_transforms.resample_coeffs; there are no per-sample host arrays.
+ * One record per sample: src[j] is the ADDRESS of the frame that feeds output position j (after the flip-swap of the views), cb[j] the
+ * per-channel brightness factors of position j; gamma / bright / cb[j][0] <= 0: transform not applied.
+ * Supported scale factors, per axis: 1 / FALNET_AUG_MAX_SCALE <= resized / source <= FALNET_AUG_MAX_SCALE, i.e. [0.5, 2.0] (at most 9
+ * taps; the reference draws from [0.75, 1.5]: at most 7).  table_dev is the record table in device memory (read by the kernel),
+ * table_host the same B records in host memory (checked before the launch): a size outside that range, a crop outside the resized image,
+ * a null operand or a source address that is not device memory is refused (falnet_last_error); there is no fallback. */
+#define FALNET_AUG_MAX_SCALE 2
+typedef struct {
+    uint64_t src[2];
+    int32_t H, W, rw, rh, x1, y1, flip, reserved;
+    double gamma, bright, cb[2][3];
+} falnet_aug_t;
+int falnet_augment_batch(const falnet_aug_t* table_dev, const falnet_aug_t* table_host, int B, int th, int tw, float mean0, float mean1,
+                         float mean2, float* out0, float* out1, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------------------
  * Host launch path in C (csrc/replay.cpp).  A command = one call of a launch entry point of this header (every function that ends in
  * `void* stream`), an event record or a stream wait.  `op`: index from falnet_replay_op_index("falnet_conv2d") ..., or FALNET_CMD_RECORD /
