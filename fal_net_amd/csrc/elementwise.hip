@@ -245,6 +245,8 @@ extern "C" int falnet_upsample_bwd(const void* gup, void* gsrc, const void* acto
                                    int C, int dtype, void* stream) {
     FALNET_ENTER(stream);
     FALNET_CHECK_ARG(gup && gsrc && B > 0 && IH >= H && IW >= W && H > 0 && W > 0 && C % 8 == 0, "upsample_bwd: bad argument");
+    // the kernel's row / column ranges ((s + 1) * I + S - 1) / S are 32-bit products
+    FALNET_CHECK_ARG((int64_t)H * IH + H <= INT32_MAX && (int64_t)W * IW + W <= INT32_MAX, "upsample_bwd: %dx%d -> %dx%d too large for 32-bit index ranges", H, W, IH, IW);
     const int64_t total = (int64_t)B * H * W * (C / 8);
 #define EW_L(T) hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(ew_grid(total)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const T*)gup, (T*)gsrc, (const T*)actout, B, IH, IW, H, W, C)
     FALNET_DISPATCH_DTYPE(dtype, EW_L);
