@@ -985,6 +985,9 @@ __global__ __launch_bounds__(256) void bias_grad_batched_kernel(const falnet_bia
     }
 }
 
+// entries per batched launch: find_entry (common.h) stages the block_begin column in a 64-int LDS array
+#define FALNET_BATCH_MAX_ENTRIES 64
+
 extern "C" int falnet_wgrad_reduce_blocks(int cout, int cin_total, int groups) {
     if (cout <= 0 || cin_total <= 0 || groups <= 0) return -1;
     const int cob = cin_total >= 1024 ? 1 : 1024 / cin_total;
@@ -993,14 +996,14 @@ extern "C" int falnet_wgrad_reduce_blocks(int cout, int cin_total, int groups) {
 
 extern "C" int falnet_wgrad_reduce_batched(const falnet_reduce_t* descs_dev, int n, int total_blocks, int accumulate, void* stream) {
     FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0, "wgrad_reduce_batched: bad argument");
+    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= FALNET_BATCH_MAX_ENTRIES && total_blocks > 0, "wgrad_reduce_batched: bad argument (n <= 64)");
     hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, accumulate ? 1 : 0);
     FALNET_RETURN_LAUNCH();
 }
 
 extern "C" int falnet_bias_grad_batched(const falnet_biasgrad_t* descs_dev, int n, int total_blocks, int dtype, void* stream) {
     FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0, "bias_grad_batched: bad argument");
+    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= FALNET_BATCH_MAX_ENTRIES && total_blocks > 0, "bias_grad_batched: bad argument (n <= 64)");
     FALNET_CHECK_ARG(!falnet_deterministic(), "bias_grad_batched: f32 atomics -- use falnet_bias_grad_batched_det in deterministic mode");
 #define BIAS_B(T) hipLaunchKernelGGL(bias_grad_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, (float*)nullptr)
     FALNET_DISPATCH_DTYPE(dtype, BIAS_B);
@@ -1011,7 +1014,7 @@ extern "C" int falnet_bias_grad_batched(const falnet_biasgrad_t* descs_dev, int 
 extern "C" int falnet_bias_grad_batched_det(const falnet_biasgrad_t* descs_dev, int n, int total_blocks, int dtype, float* ws, int64_t ws_floats,
                                             void* stream) {
     FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(descs_dev && n > 0 && total_blocks > 0 && ws, "bias_grad_batched_det: bad argument");
+    FALNET_CHECK_ARG(descs_dev && n > 0 && n <= FALNET_BATCH_MAX_ENTRIES && total_blocks > 0 && ws, "bias_grad_batched_det: bad argument (n <= 64)");
     FALNET_CHECK_ARG(ws_floats >= (int64_t)total_blocks * 512, "bias_grad_batched_det: workspace of %lld floats needed (512 per block)", (long long)total_blocks * 512);
 #define BIAS_B(T) hipLaunchKernelGGL(bias_grad_batched_kernel<T>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n, ws)
     FALNET_DISPATCH_DTYPE(dtype, BIAS_B);

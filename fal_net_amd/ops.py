@@ -843,6 +843,7 @@ class WgradBatch:
     that add into the (pre-zeroed or accumulating) flat gradient buffer."""
 
     SLAB_CAP = int(L.ab("FALNET_SLAB_CAP_MB", "32")) << 20  # bytes of partial slabs per layer
+    MAX_TABLE = 64  # entries per batched reduce / bias-gradient launch (include/falnet_hip.h: falnet_wgrad_reduce_batched)
 
     def __init__(self, dtype, device):
         self.dtype, self.device = dtype, device
@@ -897,6 +898,7 @@ class WgradBatch:
             it["partial"] = self.ws.data_ptr() + off
             off += (it["bytes"] + 255) // 256 * 256
         out, self._tables = {}, []
+        self.launches = {}  # bucket -> {"reduce": [(device table, entries, blocks), ...], "bias": [...]}: what reduce_all / bias_all issue
         code = L.dtype_code(self.dtype)
         for bucket in sorted({it["bucket"] for it in self.items}):
             all_items = [it for it in self.items if it["bucket"] == bucket]
@@ -917,46 +919,57 @@ class WgradBatch:
                 def reduce_one(one_dev=one_dev, blocks=base * groups):
                     L.check(lib.falnet_wgrad_reduce_batched(L.ptr(one_dev), 1, blocks, int(self.accumulate), L.stream_ptr()), "wgrad_reduce")
                 it["post"].append(_timed("wgrad_reduce_batched", 0, 0, reduce_one, "wgrad_reduce(layer)"))
-            red = (L.ReduceDesc * max(len(items), 1))()
-            blk = 0
-            for i, it in enumerate(items):
-                # slab groups: enough blocks to pull the slabs at the HBM rate (a block keeps <= 18 16-B loads per thread in
-                # flight), at least four slabs per group; groups > 1 makes the kernel add with atomics
-                base = lib.falnet_wgrad_reduce_blocks(it["cout"], it["cin_total"], 1)
-                groups = 1 if DETERMINISTIC else max(1, min(it["nsplit"] // 4, (_REDUCE_BLOCKS + base - 1) // base))
-                blocks = base
-                r = red[i]
-                r.partial, r.grad = it["partial"], it["grad"].data_ptr()
-                r.nsplit, r.ntaps, r.w_rows, r.cin_total = it["nsplit"], it["ntaps"], it["w_rows"], it["cin_total"]
-                r.cout, r.cin, r.c0_real, r.c0_pad, r.groups, r.block_begin = it["cout"], it["cin"], it["c0_real"], it["c0_pad"], groups, blk
-                blk += blocks * groups
-            red_dev = torch.frombuffer(bytearray(bytes(red)), dtype=torch.uint8).to(self.device)
+            # at most MAX_TABLE entries per launch (the kernels stage a table's block_begin column in a 64-int LDS array; the library
+            # refuses longer tables): a bucket with more weight tensors / biases takes several launches, each with its own table
+            red_launches = []  # (device table, entries, blocks)
+            for first in range(0, len(items), self.MAX_TABLE):
+                part = items[first:first + self.MAX_TABLE]
+                red = (L.ReduceDesc * len(part))()
+                blk = 0
+                for i, it in enumerate(part):
+                    # slab groups: enough blocks to pull the slabs at the HBM rate (a block keeps <= 18 16-B loads per thread in
+                    # flight), at least four slabs per group; groups > 1 makes the kernel add with atomics
+                    base = lib.falnet_wgrad_reduce_blocks(it["cout"], it["cin_total"], 1)
+                    groups = 1 if DETERMINISTIC else max(1, min(it["nsplit"] // 4, (_REDUCE_BLOCKS + base - 1) // base))
+                    r = red[i]
+                    r.partial, r.grad = it["partial"], it["grad"].data_ptr()
+                    r.nsplit, r.ntaps, r.w_rows, r.cin_total = it["nsplit"], it["ntaps"], it["w_rows"], it["cin_total"]
+                    r.cout, r.cin, r.c0_real, r.c0_pad, r.groups, r.block_begin = it["cout"], it["cin"], it["c0_real"], it["c0_pad"], groups, blk
+                    blk += base * groups
+                red_launches.append((torch.frombuffer(bytearray(bytes(red)), dtype=torch.uint8).to(self.device), len(part), blk))
             biases = [b for b in self.bias if b["bucket"] == bucket]
-            bias = (L.BiasGradDesc * max(len(biases), 1))()
-            bblk = 0
-            for i, it in enumerate(biases):
-                segs = it["gC"] // 8
-                rows = 256 // min(segs, 256)
-                blocks = int(max(1, min(256, (it["npix"] + rows * 64 - 1) // (rows * 64))))
-                b = bias[i]
-                b.g, b.db, b.npix, b.gC, b.cout, b.blocks, b.block_begin = it["g"].data_ptr(), it["db"].data_ptr(), it["npix"], it["gC"], it["cout"], blocks, bblk
-                bblk += blocks
-            bias_dev = torch.frombuffer(bytearray(bytes(bias)), dtype=torch.uint8).to(self.device)
-            self._tables += [red_dev, bias_dev]
+            bias_launches = []
+            for first in range(0, len(biases), self.MAX_TABLE):
+                part = biases[first:first + self.MAX_TABLE]
+                bias = (L.BiasGradDesc * len(part))()
+                bblk = 0
+                for i, it in enumerate(part):
+                    segs = it["gC"] // 8
+                    rows = 256 // min(segs, 256)
+                    blocks = int(max(1, min(256, (it["npix"] + rows * 64 - 1) // (rows * 64))))
+                    b = bias[i]
+                    b.g, b.db, b.npix, b.gC, b.cout, b.blocks, b.block_begin = it["g"].data_ptr(), it["db"].data_ptr(), it["npix"], it["gC"], it["cout"], blocks, bblk
+                    bblk += blocks
+                bias_launches.append((torch.frombuffer(bytearray(bytes(bias)), dtype=torch.uint8).to(self.device), len(part), bblk))
+            self._tables += [t for t, _, _ in red_launches + bias_launches]
+            self.launches[bucket] = {"reduce": red_launches, "bias": bias_launches}
 
-            def reduce_all(red_dev=red_dev, n=len(items), blocks=blk):
-                if n:
+            def reduce_all(red_launches=red_launches):
+                for red_dev, n, blocks in red_launches:
                     L.check(lib.falnet_wgrad_reduce_batched(L.ptr(red_dev), n, blocks, int(self.accumulate), L.stream_ptr()), "wgrad_reduce_batched")
 
-            bias_ws = torch.empty(max(bblk, 1) * 512, dtype=torch.float32, device=self.device) if DETERMINISTIC and biases else None
+            # deterministic mode: per-block partials, added in block order; the launches of a bucket are stream-ordered and share the workspace
+            bias_ws = (torch.empty(max(b for _, _, b in bias_launches) * 512, dtype=torch.float32, device=self.device)
+                       if DETERMINISTIC and bias_launches else None)
             self._tables.append(bias_ws)
 
-            def bias_all(bias_dev=bias_dev, n=len(biases), blocks=bblk, bias_ws=bias_ws):
-                if n and bias_ws is not None:  # deterministic mode: per-block partials, added in block order
-                    L.check(lib.falnet_bias_grad_batched_det(L.ptr(bias_dev), n, blocks, code, L.ptr(bias_ws), bias_ws.numel(), L.stream_ptr()),
-                            "bias_grad_batched_det")
-                elif n:
-                    L.check(lib.falnet_bias_grad_batched(L.ptr(bias_dev), n, blocks, code, L.stream_ptr()), "bias_grad_batched")
+            def bias_all(bias_launches=bias_launches, bias_ws=bias_ws):
+                for bias_dev, n, blocks in bias_launches:
+                    if bias_ws is not None:
+                        L.check(lib.falnet_bias_grad_batched_det(L.ptr(bias_dev), n, blocks, code, L.ptr(bias_ws), bias_ws.numel(), L.stream_ptr()),
+                                "bias_grad_batched_det")
+                    else:
+                        L.check(lib.falnet_bias_grad_batched(L.ptr(bias_dev), n, blocks, code, L.stream_ptr()), "bias_grad_batched")
             out[bucket] = (_timed("wgrad_reduce_batched", 0, 0, reduce_all, "wgrad_reduce_batched"),
                            _timed("bias_grad_batched", 0, 0, bias_all, "bias_grad_batched"))
         return out

@@ -298,7 +298,13 @@ typedef struct {
 } falnet_pack_up2_t;
 int falnet_pack_up2_batched(const falnet_pack_up2_t* descs_dev, int n, int total_blocks, int dtype, void* stream);
 /* accumulate == 0: entries with groups == 1 OVERWRITE their gradient (plain stores), entries with groups > 1 add into it
- * (atomics: the caller zeroes those); accumulate != 0: every entry adds */
+ * (atomics: the caller zeroes those); accumulate != 0: every entry adds.
+ * Limits of the three batched entry points below: at most 64 entries per launch (n > 64 is refused before anything is launched: the
+ * kernels stage the block_begin column of the table in a 64-int LDS array; fal_net_amd.ops.WgradBatch cuts longer tables into several
+ * launches).  The tables live in DEVICE memory, so the library cannot check their fields: a falnet_biasgrad_t entry must have gC a
+ * multiple of 32 with gC <= 2048 (beyond that the kernel's channel-segment loop reaches a workgroup barrier with some threads missing
+ * when gC / 8 is not a multiple of 256) and cout <= 512 (the deterministic form's workspace has 512 columns per block; its finishing
+ * kernel has 512 threads); a falnet_reduce_t entry has ntaps in {1, 3, 9}, cin_total a multiple of 32, 1 <= groups <= nsplit. */
 int falnet_wgrad_reduce_batched(const falnet_reduce_t* descs_dev, int n, int total_blocks, int accumulate, void* stream);
 int falnet_bias_grad_batched(const falnet_biasgrad_t* descs_dev, int n, int total_blocks, int dtype, void* stream);
 /* the same sums without atomics: every block stores its partial sums to ws[block][512] (ws_floats >= 512 * total_blocks, channels
