@@ -51,7 +51,7 @@ class Conv(C.Structure):
                 ("actout_kind", C.c_int32), ("dtype", C.c_int32), ("ksplit", C.c_int32), ("splitk_ws", C.c_void_p),
                 ("splitk_ws_bytes", C.c_int64), ("variant", C.c_int32), ("pool_out", C.c_void_p),
                 ("pool_mode", C.c_int32), ("pool_actout_kind", C.c_int32), ("pool_actout", C.c_void_p), ("weight_up2", C.c_void_p),
-                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64), ("pool_code", C.c_void_p)]
 
 
 class Wgrad(C.Structure):
@@ -135,6 +135,7 @@ SIGNATURES = {
     "falnet_wgrad_const_plane": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "falnet_maxpool2_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "falnet_maxpool2_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "falnet_maxpool2_bwd_codes": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "falnet_act_bwd": [_P, _P, _P, _L, _I, _I, _P],
     "falnet_med_head_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_head_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -1678,6 +1678,12 @@ static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
         }
         variant = 1;
     }
+    if (p.pool_code && !(variant == 23 && p.dtype != FALNET_F32 && p.pool_out && p.pool_mode == 0 && !planar && p.OH % 2 == 0 && p.OW % 2 == 0 &&
+                         p.Cout % 32 == 0 && p.out_cstride % 32 == 0)) {
+        falnet_set_error("conv2d: pool_code (argmax codes of the fused max pool) needs variant 23, a 16-bit type, pool_out with pool_mode 0, an NHWC "
+                         "launch with even OH / OW and whole 32-channel groups (variant %d, dtype %d, pool_mode %d)", p.variant, p.dtype, p.pool_mode);
+        return -2;
+    }
     if (g_disable_patch) variant = 1;
     switch (variant) {  // the accepted variants; what each one selects follows below
         case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7: case 8: case 9: case 10:
@@ -1964,7 +1970,10 @@ static const ConvFamilyRow conv_families[] = {
     {ConvFamily::Up2Dma, SYMBOL("_Z22conv3x3_up2_dma_kernelI%sEv13falnet_conv_tiiiii", t), LAUNCH(falnet_conv_up2_dma_launch(p, st))},
     {ConvFamily::Deep, SYMBOL("_Z19conv3x3_deep_kernelI%sLi%dELi%dEEv13falnet_conv_t18falnet_deep_geom_t", t, c.kcb, c.nwaves), LAUNCH(falnet_conv_deep_launch(p, st))},
     {ConvFamily::Dma2, SYMBOL("_Z19conv3x3_dma2_kernelI%sLb%dELi%dEEv13falnet_conv_tiiiii", t, p.pool_out ? 1 : 0, c.nwaves), LAUNCH(falnet_conv_dma2_launch(p, c.flip, st, c.th))},
-    {ConvFamily::Dma16, SYMBOL("_Z20conv3x3_dma16_kernelI%sLb%dELi%dELi%dELb%dEEv13falnet_conv_tiiii", t, p.pool_out ? 1 : 0, c.th, c.nwaves, p.out_layout == FALNET_OUT_PLANAR_F32 ? 1 : 0),
+    {ConvFamily::Dma16, [](char* buf, int len, const char* t, const falnet_conv_t& p, const ConvChoice& c) {
+         if (p.pool_out && p.pool_code) return snprintf(buf, len, "_Z20conv3x3_dma16_kernelI9PoolCodesI%sELb1ELi16ELi8ELb0EEv13falnet_conv_tiiii", t);
+         return snprintf(buf, len, "_Z20conv3x3_dma16_kernelI%sLb%dELi%dELi%dELb%dEEv13falnet_conv_tiiii", t, p.pool_out ? 1 : 0, c.th, c.nwaves, p.out_layout == FALNET_OUT_PLANAR_F32 ? 1 : 0);
+     },
      LAUNCH(falnet_conv_dma16_launch(p, c.flip, st, c.th))},
     {ConvFamily::Up2d, SYMBOL("_Z25conv2x2_up2d_dma16_kernelI%sEv13falnet_conv_tiii", t), LAUNCH(falnet_conv_up2d_launch(p, st))},
     {ConvFamily::Wave32, SYMBOL("_Z21conv3x3_wave32_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave32_launch(p, c.flip, st))},

@@ -691,8 +691,16 @@ int falnet_conv_dma2_launch(const falnet_conv_t& p, int flip, hipStream_t st, in
 // <T, POOL, 16, 8, PLANAR>: variant 23 (PLANAR: the planar-f32 output form of the logits launch, an instantiation of its own -- its sixteen 64-bit
 // store addresses cost ~60 registers).  <T, false, 4, 4, false> / <T, false, 8, 8, false>: variants 24 / 25, the 4 x 32 / 8 x 32 tiles of variants
 // 17 / 20 (one row per wave) for the maps of levels 4 / 3.
-template <typename T, bool POOL, int TH, int NWAVES, bool PLANAR>
+// <PoolCodes<T>, true, 16, 8, false>: the <T, true, 16, 8, false> program whose fused max pool also writes p.pool_code (conv_epilogue.h: CODES).  The
+// switch rides on the operand TYPE so that it is an instantiation of its own and every other one keeps its symbol and its code: <T, true, 16, 8, false>
+// also serves the label pass and the dgrad + 2x2-sum launches at 209-224 registers, two waves per SIMD, and gets no run-time branch.
+template <typename T> struct PoolCodes {};
+template <typename TT> struct Dma16Operand { typedef TT type; static constexpr bool codes = false; };
+template <typename T> struct Dma16Operand<PoolCodes<T>> { typedef T type; static constexpr bool codes = true; };
+template <typename TT, bool POOL, int TH, int NWAVES, bool PLANAR>
 __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 2 : 1) void conv3x3_dma16_kernel(const falnet_conv_t p, int tiles_x, int tiles_y, int flip, int ntiles) {
+    typedef typename Dma16Operand<TT>::type T;
+    constexpr bool CODES = Dma16Operand<TT>::codes;
     constexpr int MT = TH / NWAVES, BN = 64, NT = BN / 32;
     static_assert(sizeof(T) == 2 && (MT == 1 || MT == 2) && (MT == 2 || !POOL), "16-bit operands; one or two rows per wave; the fused pool needs row pairs");
     constexpr int KCV = 32;
@@ -965,7 +973,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 2 : 1) void conv3x3_dma1
                     acc[mt][nt].to32(v[mt][0]);
                     acc[mt][nt].zero();
                 }
-                if constexpr (POOL) epilogue_direct<T, MT, 1, decltype(pixoff), decltype(pooloff), -1, false, true>(p, v, bias, n0 + 32 * nt, lane, pixoff, pooloff);
+                if constexpr (POOL) epilogue_direct<T, MT, 1, decltype(pixoff), decltype(pooloff), -1, false, true, false, CODES>(p, v, bias, n0 + 32 * nt, lane, pixoff, pooloff);
                 else epilogue_direct<T, MT, 1, decltype(pixoff), NoPool, (PLANAR ? -1 : FALNET_DMA16_EPI_AHEAD), false, !PLANAR, PLANAR>(p, v, bias, n0 + 32 * nt, lane, pixoff);
                 if (nt == 0) CD16_B();  // B 4: slice 0 done
             }
@@ -994,6 +1002,7 @@ int falnet_conv_dma16_launch(const falnet_conv_t& p, int flip, hipStream_t st, i
         if (th == 4) DMA16_K(T, false, 4, 4, false);      \
         else if (th == 8) DMA16_K(T, false, 8, 8, false); \
         else if (planar) DMA16_K(T, false, 16, 8, true);  \
+        else if (p.pool_out && p.pool_code) DMA16_K(PoolCodes<T>, true, 16, 8, false); \
         else if (p.pool_out) DMA16_K(T, true, 16, 8, false); \
         else DMA16_K(T, false, 16, 8, false);             \
     } while (0)

@@ -304,7 +304,19 @@ __device__ __forceinline__ float lane_xor1(float v) {  // value of lane ^ 1 (DPP
 // ~60 registers at a kernel's high-water mark even when the branch is never taken.
 // PLANAR_PTR: the planar-f32 stores walk ONE running 64-bit pointer (channel stride added between stores, pinned by an empty asm) instead of sixteen
 // independent addresses: 2 address registers instead of 32 (conv3x3_dma16_kernel's planar instantiation spilled 136 B per lane without it).
-template <typename T, int MT, int NT, typename PixOff, typename PoolOff = NoPool, int AHEAD = 1, bool DEFER = false, bool NHWC_ONLY = false, bool PLANAR_PTR = false>
+// CODES (fused max pool, 16-bit types, not DEFER): the pooled map is written as without it and p.pool_code gets one 4-bit argmax code per pooled
+// element -- what the pool's backward needs of the full-resolution map, so that `out` may be NULL on a gradient-carrying pass.
+//   code = one-hot nibble, bit 2 * row + column of the window element that receives the gradient; 0 when the pooled value is not > 0.
+//   layout: [B][OH/2][OW/2][out_cstride / 2] bytes, channel c of a pooled pixel in byte c / 2, low nibble for even c (the pooled map's own order).
+// The winner is the FIRST maximum of the window in row-major order under strict > comparisons on the values as rounded to T (the rule of
+// maxpool2_bwd_kernel, elementwise.hip): v is rounded BEFORE the pool (rounding is monotonic, so max commutes with it and the pooled map keeps its
+// bits).  Evaluated pair-wise -- right[row] = (x[row][1] > x[row][0]) per row and lower = (max of row 1 > max of row 0) -- this is the sequential
+// scan a, b, c, d with `if (v > best)`: when lower holds, the maximum lies in row 1 only and its first occurrence there is c unless d > c; otherwise
+// the maximum occurs in row 0, every element of which precedes row 1, and its first occurrence is a unless b > a.
+// A lane holds the nibbles of its 16 channels (accumulator order) in two dwords; one half swap and two byte permutes put them into channel order,
+// and every even lane stores 8 bytes: channels cbase + 16 h .. + 15.
+template <typename T, int MT, int NT, typename PixOff, typename PoolOff = NoPool, int AHEAD = 1, bool DEFER = false, bool NHWC_ONLY = false, bool PLANAR_PTR = false,
+          bool CODES = false>
 __device__ __forceinline__ void epilogue_direct(const falnet_conv_t& p, f32x16 (&acc)[MT][NT], const float (&bias)[NT][16], int nbase, int lane,
                                                 PixOff pixoff, PoolOff pooloff = PoolOff(), PackedOut<T, MT, NT>* defer = nullptr) {
     constexpr bool POOL = !std::is_same<PoolOff, NoPool>::value;
@@ -319,6 +331,7 @@ __device__ __forceinline__ void epilogue_direct(const falnet_conv_t& p, f32x16 (
     for (int nt = 0; nt < NT; ++nt) {
         const int cbase = nbase + nt * 32;
         float hp[16];
+        [[maybe_unused]] bool top_right[CODES ? 16 : 1];  // CODES: right[] of the pair's even row
         // residual / activation-output operands: fetched one row slab AHEAD (branch-free loads, conv_epilogue.h: tile_fetch), so their latency
         // sits behind the previous slab's arithmetic and stores instead of in front of every 16-B load
         constexpr int NR = AHEAD < 0 ? 1 : 1 + AHEAD;
@@ -352,6 +365,10 @@ __device__ __forceinline__ void epilogue_direct(const falnet_conv_t& p, f32x16 (
                 else tile_unpack<T>(rb[mt & (AHEAD < 0 ? 0 : AHEAD)], a);
                 actgrad16(v, a, p.actout_kind);
             }
+            if constexpr (CODES) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = to_f32(from_f32<T>(v[j]));  // the stored value: the pool compares what its backward would read
+            }
             if constexpr (DEFER) {
                 tile_pack<T>(v, defer->out[mt][nt]);
             } else if (!NHWC_ONLY && p.out_layout == FALNET_OUT_PLANAR_F32) {
@@ -378,7 +395,43 @@ __device__ __forceinline__ void epilogue_direct(const falnet_conv_t& p, f32x16 (
                     }
                 }
             } else if (!POOL || out) tile_store<T>(out, o, cbase, h, p.Cout, v);
-            if constexpr (POOL) {
+            if constexpr (POOL && CODES) {
+                static_assert(!DEFER && sizeof(T) == 2 && MT % 2 == 0, "argmax codes: direct stores, 16-bit types, row pairs");
+                if (pooling) {  // (pool_mode 0 and p.pool_code set: choose_conv_kernel)
+                    float m[16];
+                    bool right[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const float n = lane_xor1(v[j]);  // column neighbour: the RIGHT one on the even lanes, which alone store
+                        right[j] = n > v[j];
+                        m[j] = fmaxf(v[j], n);
+                    }
+                    if ((mt & 1) == 0) {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            hp[j] = m[j];
+                            top_right[j] = right[j];
+                        }
+                    } else {
+                        unsigned cw[2] = {0u, 0u};  // nibble of accumulator j in bits 4 (j & 7) of word j >> 3
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const bool lower = m[j] > hp[j];
+                            m[j] = fmaxf(m[j], hp[j]);
+                            const unsigned nib = m[j] > 0.f ? (lower ? (right[j] ? 8u : 4u) : (top_right[j] ? 2u : 1u)) : 0u;
+                            cw[j >> 3] |= nib << (4 * (j & 7));
+                        }
+                        const int64_t po = (lane & 1) ? (int64_t)-1 : pooloff(mt);
+                        tile_store<T>(pool_out, po, cbase, h, p.Cout, m);
+                        // accumulator j = channel 8 (j >> 2) + 4 h + (j & 3): after the half swap the lower lane holds the words of channels 0-15 of both
+                        // halves, the upper lane those of channels 16-31; interleaving their 16-bit pieces gives channel order
+                        half_swap(cw[0], cw[1]);
+                        const unsigned c0 = (cw[0] & 0xffffu) | (cw[1] << 16), c1 = (cw[0] >> 16) | (cw[1] & 0xffff0000u);
+                        if (po >= 0 && cbase + 16 * h < p.Cout)
+                            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(p.pool_code) + (po >> 1) + (cbase >> 1) + 8 * h) = make_uint2(c0, c1);
+                    }
+                }
+            } else if constexpr (POOL) {
                 if (pooling) {
                     float m[16];
                     if (psum) {

@@ -204,6 +204,31 @@ __global__ __launch_bounds__(EW_THREADS) void maxpool2_bwd_vec_kernel(const T* _
     }
 }
 
+// The same routing from the 4-bit argmax codes the fused pool wrote (falnet_conv_t::pool_code: one-hot nibble, bit 2 * row + column of the winner,
+// 0 = no gradient; channel c of a pooled pixel in byte c / 2, low nibble for even c): the full-resolution map is neither kept nor re-read.
+// One thread = 8 channels of one window: 4 B of codes, 16 B of gy (two for f32), four 16-B stores -- every element of gx is written.
+template <typename T>
+__global__ __launch_bounds__(EW_THREADS) void maxpool2_bwd_codes_kernel(const unsigned char* __restrict__ codes, const T* __restrict__ gy,
+                                                                        T* __restrict__ gx, int B, int H, int W, int C) {
+    const int OH = H / 2, OW = W / 2, cg = C / 8;
+    const int64_t total = (int64_t)B * OH * OW * cg;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % cg) * 8, ox = (int)((i / cg) % OW), oy = (int)((i / ((int64_t)cg * OW)) % OH);
+        const int b = (int)(i / ((int64_t)cg * OW * OH));
+        const int64_t base = (((int64_t)b * H + 2 * oy) * W + 2 * ox) * C + c0;
+        const int64_t off[4] = {0, C, (int64_t)W * C, (int64_t)W * C + C};
+        const unsigned code = *reinterpret_cast<const unsigned*>(codes + i * 4);  // (i enumerates (pooled pixel, 8-channel group) in memory order)
+        float g[8], o[4][8];
+        load8_as(gy + (((int64_t)b * OH + oy) * OW + ox) * C + c0, g);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j][e] = ((code >> (4 * e + j)) & 1u) ? g[e] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) store8_as(gx + base + off[j], o[j]);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(EW_THREADS) void act_bwd_kernel(const T* __restrict__ g, const T* __restrict__ y,
                                                              T* __restrict__ gx, int64_t n, int kind) {
@@ -397,6 +422,20 @@ extern "C" int falnet_maxpool2_bwd(const void* x, const void* y, const void* gy,
     }
     const int64_t total = (int64_t)B * (H / 2) * (W / 2) * C;
 #define EW_L(T) hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(ew_grid(total)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, (T*)gx, B, H, W, C)
+    FALNET_DISPATCH_DTYPE(dtype, EW_L);
+#undef EW_L
+    FALNET_RETURN_LAUNCH();
+}
+
+extern "C" int falnet_maxpool2_bwd_codes(const void* codes, const void* gy, void* gx, int B, int H, int W, int C, int dtype, void* stream) {
+    FALNET_ENTER(stream);
+    FALNET_CHECK_ARG(codes && gy && gx && B > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && C > 0,
+                     "maxpool2_bwd_codes: bad argument (even H, W required)");
+    FALNET_CHECK_ARG(dtype == FALNET_F32 || dtype == FALNET_BF16 || dtype == FALNET_F16, "maxpool2_bwd_codes: bad dtype %d", dtype);
+    FALNET_CHECK_ARG(C % 8 == 0 && (((uintptr_t)gy | (uintptr_t)gx) & 15) == 0 && ((uintptr_t)codes & 3) == 0,
+                     "maxpool2_bwd_codes: C must be a multiple of 8, gy / gx 16-B and codes 4-B aligned");
+    const int64_t tv = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
+#define EW_L(T) hipLaunchKernelGGL(maxpool2_bwd_codes_kernel<T>, dim3(ew_grid(tv)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const unsigned char*)codes, (const T*)gy, (T*)gx, B, H, W, C)
     FALNET_DISPATCH_DTYPE(dtype, EW_L);
 #undef EW_L
     FALNET_RETURN_LAUNCH();

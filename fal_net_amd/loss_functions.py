@@ -43,11 +43,18 @@ def _release_plan(plan, gen):
 class _VggPlan:
     """Static launch plan of VGG19 features[0:19] forward + data-gradient for one (B,H,W,dtype)."""
 
-    def __init__(self, owner, B, H, W, dtype, device, need_grad=True):
+    def __init__(self, owner, B, H, W, dtype, device, need_grad=True, pool_codes=None, pool_variant=None):
         """need_grad=False (label features, Train_Stage1_K.py:241-244 under no_grad): the convs in front of a pool keep only
-        their pooled map (fused pool, no full-resolution store) and no backward launches are built."""
+        their pooled map (fused pool, no full-resolution store) and no backward launches are built.
+        pool_codes (need_grad=True; None = the FALNET_POOL_CODES experiment switch, on by default): the conv in front of a pool keeps its pooled map
+        and one 4-bit argmax code per pooled element (falnet_conv_t::pool_code) instead of the full-resolution map, whose only reader was the pool's
+        backward; per slice, where the kernel does not apply (f32, maps under 16 x 32) the full-resolution form is built as before.
+        pool_variant: forced falnet_conv2d variant of those convs in the full-resolution form (tests: the same kernel on both sides)."""
         self.B, self.H, self.W, self.dtype, self.device = B, H, W, dtype, device
         self.busy, self.need_grad, self.gen = False, need_grad, 0
+        if pool_codes is None:
+            pool_codes = L.ab("FALNET_POOL_CODES", "1") == "1"
+        self.pool_maps, self.pool_codes = [], []  # per slice: the full-resolution map in front of the pool / its argmax codes (one of them is None)
         code = L.dtype_code(dtype)
         self.fwd, self.bwd = [], []
         _conv = lambda *a, **kw: ops.conv_call(*a, ws_owner=("vgg", id(self)), **kw)  # own split-K scratch per plan instance
@@ -62,16 +69,27 @@ class _VggPlan:
                 pc = pcs[idx]
                 last = idx == convs[-1]
                 pooled = torch.empty(B, h // 2, w // 2, pc.cout, dtype=dtype, device=device) if last else None
-                y = torch.empty(B, h, w, pc.cout, dtype=dtype, device=device) if (need_grad or not last) else None
+                codes = None
                 kw = dict(bias=pc.bias, act=L.ACT_RELU, name=f"vgg conv{idx}", flops=2 * B * h * w * pc.cout * pc.cin * 9)
                 args = (dtype, [ops.nhwc_src(cur)], h, w, pc.wf, pc.cin_pad, ops.fwd_taps(3), 9, pc.cout_pad, 1, B, h, w)
                 fused = False
-                if cur is x0:
+                fuse_pool = last and cur is not x0 and L.ab("FALNET_FUSED_POOL", "1") == "1"
+                if fuse_pool and need_grad and pool_codes:
+                    try:  # pooled map + argmax codes from the epilogue: no full-resolution store, nothing for the pool's backward to re-read
+                        codes = torch.empty(B, h // 2, w // 2, pc.cout // 2, dtype=torch.uint8, device=device)
+                        self.fwd.append(_conv(*args, None, h, w, pc.cout, pc.cout, pool_out=pooled, pool_code=codes, variant=23, **kw))
+                        fused = True
+                    except ValueError:
+                        codes = None
+                y = torch.empty(B, h, w, pc.cout, dtype=dtype, device=device) if ((need_grad and codes is None) or not last) else None
+                if fused:
+                    pass
+                elif cur is x0:
                     self.c3_call = ops.conv_c3_call(dtype, x_in, pc, y, L.ACT_RELU, name="vgg conv0(c3)")
                     self.fwd.append(self.c3_call)
-                elif last and L.ab("FALNET_FUSED_POOL", "1") == "1":
+                elif fuse_pool:
                     try:  # 2x2 max pool in the conv epilogue: the full-resolution map is not re-read (nor written at all for labels)
-                        self.fwd.append(_conv(*args, y, h, w, pc.cout, pc.cout, pool_out=pooled, **kw))
+                        self.fwd.append(_conv(*args, y, h, w, pc.cout, pc.cout, pool_out=pooled, variant=pool_variant if need_grad else None, **kw))
                         fused = True
                     except ValueError:
                         pass
@@ -83,7 +101,9 @@ class _VggPlan:
                     self.fwd.append(ops.simple_call("falnet_maxpool2_fwd", L.ptr(y), L.ptr(pooled), B, h, w, pc.cout, code))
                 acts.append((pc, cur, y, h, w))
                 cur = y
-            acts.append(("pool", cur, pooled, h, w))
+            acts.append(("pool", cur, pooled, h, w, codes))
+            self.pool_maps.append(cur)
+            self.pool_codes.append(codes)
             self.outs.append(pooled)
             cur, h, w = pooled, h // 2, w // 2
         self.run_fwd = ops.ReplayList(self.fwd, eager_head=1)  # (the first conv reads the caller's image: set_input per call)
@@ -99,13 +119,17 @@ class _VggPlan:
         slice_i = len(self.outs) - 1
         for entry in reversed(acts):
             if entry[0] == "pool":
-                _, x, pooled, h, w = entry
+                _, x, pooled, h, w, codes = entry
                 # deeper slices feed back into this pooled output: their data gradient already holds the sum (the conv below
                 # this pool took the slice's own gradient as its epilogue addend), the deepest slice has only its own
                 gy = self.gouts[slice_i] if g_next is None else g_next
-                gx = torch.empty_like(x)  # gradient wrt the pre-ReLU conv output feeding the pool (relu' fused)
-                self.bwd.append(ops.simple_call("falnet_maxpool2_bwd", L.ptr(x), L.ptr(pooled), L.ptr(gy), L.ptr(gx), B, h, w,
-                                                x.shape[3], code))
+                ch = pooled.shape[3]
+                gx = torch.empty(B, h, w, ch, dtype=dtype, device=device)  # gradient wrt the pre-ReLU conv output feeding the pool (relu' fused)
+                if codes is not None:
+                    self.bwd.append(ops.simple_call("falnet_maxpool2_bwd_codes", L.ptr(codes), L.ptr(gy), L.ptr(gx), B, h, w, ch, code))
+                    self.keep.append(codes)
+                else:
+                    self.bwd.append(ops.simple_call("falnet_maxpool2_bwd", L.ptr(x), L.ptr(pooled), L.ptr(gy), L.ptr(gx), B, h, w, ch, code))
                 g_next, slice_i = gx, slice_i - 1
                 self.keep.append(gx)
             else:

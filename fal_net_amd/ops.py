@@ -380,10 +380,11 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
               Cout, out_cstride, out_layout=L.OUT_NHWC, out_step=(1, 1, 0, 0), bias=None, addend=None,
               act=L.ACT_NONE, actout=None, actout_kind=L.ACT_NONE, weight_offset_elems=0, name="conv", flops=0,
               autotune=True, ws_owner=None, pool_out=None, pool_mode=0, pool_actout=None, pool_actout_kind=L.ACT_NONE, weight_up2=None,
-              variant=None):
+              variant=None, pool_code=None):
     """Build one falnet_conv2d launch; returns a zero-argument callable.  `pool_out`: fused 2x2 max pool of the output
     (halo-patch kernels only; `out` may then be None when only the pooled map is needed).  `variant`: this kernel and no other (no autotune;
-    ValueError when it does not apply)."""
+    ValueError when it does not apply).  `pool_code`: uint8 [B, OH/2, OW/2, out_cstride/2] for the pool's 4-bit argmax codes (falnet_conv_t::pool_code:
+    variant 23 only, so pass variant=23; not part of conv_signature -- a forced variant makes no cache entry)."""
     lib = L.lib()
     d = L.Conv()
     d.nsrc = len(srcs)
@@ -401,6 +402,7 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
     d.pool_mode, d.pool_actout_kind = pool_mode, pool_actout_kind
     d.pool_actout = 0 if pool_actout is None else pool_actout.data_ptr()
     d.weight_up2 = 0 if weight_up2 is None else weight_up2.data_ptr()
+    d.pool_code = 0 if pool_code is None else pool_code.data_ptr()
     dev_t = out if out is not None else pool_out
     d.bias = 0 if bias is None else bias.data_ptr()
     d.addend = 0 if addend is None else addend.data_ptr()
@@ -418,7 +420,7 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
         scratch = _deep_scratch(dev_t.device, ws_owner)
         d.scratch, d.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
     ref = C.byref(d)
-    keep = (d, srcs, weight, out, bias, addend, actout, ws, pool_out, pool_actout, weight_up2, scratch)
+    keep = (d, srcs, weight, out, bias, addend, actout, ws, pool_out, pool_actout, weight_up2, scratch, pool_code)
     if variant is not None:
         d.variant = variant
         if lib.falnet_conv2d_kernel_name(ref, C.create_string_buffer(160), 160) != 0:

@@ -164,6 +164,11 @@ typedef struct {
                                   ksplit * ceil(B TH TW / 128 | 256) * 128 | 256 * w_rows f32; contents are meaningless between launches;
                                   launches that share it must be stream-ordered */
     int64_t scratch_bytes;
+    void* pool_code;           /* optional, variant 23 with pool_out and pool_mode 0 in a 16-bit type only (-2 otherwise): one 4-bit argmax code per
+                                  pooled element, [B][OH/2][OW/2][out_cstride / 2] bytes, channel c in byte c / 2 (low nibble: even c).  The code is
+                                  one-hot: bit 2 * row + column of the window element that is the FIRST maximum in row-major order (strict >, on the
+                                  values as rounded to `dtype`), 0 when the pooled value is not > 0 -- all that falnet_maxpool2_bwd_codes needs, so
+                                  `out` may stay NULL on a gradient-carrying pass.  Private to these two entry points */
 } falnet_conv_t;
 int falnet_conv2d(const falnet_conv_t* p, void* stream);
 /* First layer: 3x3 / stride 1 / pad 1 convolution of a 3-channel planar f32 image (FAL_netB.py:99 conv0, VGG19 features[0];
@@ -343,6 +348,10 @@ int falnet_wgrad_const_plane(const void* gout, const void* plane, int64_t plane_
 int falnet_maxpool2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int falnet_maxpool2_bwd(const void* x, const void* y, const void* gy, void* gx, int B, int H, int W, int C,
                         int dtype, void* stream);
+/* maxpool2_bwd_codes: the same gradient from the argmax codes a fused pool wrote (falnet_conv_t::pool_code, [B][H/2][W/2][C/2] bytes) instead of
+ * the pool input: every element of gx [B][H][W][C] is written, gy where the window's code selects it and zero elsewhere.  H, W even,
+ * C % 8 == 0, gy / gx 16-B aligned (-1 otherwise: there is no scalar form). */
+int falnet_maxpool2_bwd_codes(const void* codes, const void* gy, void* gx, int B, int H, int W, int C, int dtype, void* stream);
 /* maxpool2_bwd: x is the (ReLU) pool input; the gradient goes to the first maximum of each window
  * (aten tie rule) and is zero where that maximum is 0 (fused relu'); H, W even. */
 /* gx = g * act'(y) elementwise on NHWC, act' from the activation OUTPUT y (ELU: y>0?1:y+1) */

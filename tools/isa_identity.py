@@ -1,11 +1,16 @@
 """Compare the gfx950 instruction streams of two source trees, kernel by kernel.
 
     python tools/isa_identity.py emit <tree> <outdir>       # compile every .hip of _build.SOURCES to <outdir>/<file>.s
-    python tools/isa_identity.py compare <dirA> <dirB> [--allow REGEX]
+    python tools/isa_identity.py compare <dirA> <dirB> [--allow REGEX] [--kernarg]
 
 emit uses the tree's own _build.FLAGS / FILE_FLAGS plus --offload-device-only -S.  compare splits each .s at the kernel
 symbols (`_Z...:` to `.Lfunc_end`), drops comments and normalises the function-numbered local labels, then reports the
-symbol sets and every kernel whose body differs.  Exit status 1 if a kernel outside --allow differs or the symbol sets do.
+symbol sets and every kernel whose body differs.  Exit status 1 if a kernel outside --allow differs or a symbol of A is missing in B or
+a symbol outside --allow is new in B.
+--kernarg: a field appended to a struct that kernels take BY VALUE (falnet_conv_t) moves every argument behind it and the hidden arguments:
+the kernel-argument loads change their offsets and nothing else.  With this switch the scalar instructions that carry such an offset
+(s_load_*, s_add_u32 / s_addc_u32, s_mul*) and the .amdhsa_kernarg_size directive are compared with their numbers masked; every other line
+(all vector, MFMA, LDS and memory instructions, all branches) still has to match exactly, and the count of masked-only kernels is reported.
 """
 import importlib.util
 import os
@@ -58,8 +63,21 @@ def kernels(d):
     return out
 
 
-def compare(a, b, allow):
+_KERNARG_LINE = re.compile(r"^\s*(s_load_dword\w*|s_add_u32|s_addc_u32|s_mul\w*|\.amdhsa_kernarg_size)\b")
+_NUMBER = re.compile(r"0x[0-9a-f]+|\b\d+\b")
+
+
+def mask_kernarg(body):
+    return "\n".join(_NUMBER.sub("N", line) if _KERNARG_LINE.match(line) else line for line in body.split("\n"))
+
+
+def compare(a, b, allow, kernarg=False):
     ka, kb = kernels(a), kernels(b)
+    if kernarg:
+        exact = sum(1 for s in set(ka) & set(kb) if ka[s] == kb[s])
+        ka, kb = {s: mask_kernarg(v) for s, v in ka.items()}, {s: mask_kernarg(v) for s, v in kb.items()}
+        same = sum(1 for s in set(ka) & set(kb) if ka[s] == kb[s])
+        print(f"--kernarg: {exact} bodies identical as they are, {same - exact} more once the kernel-argument offsets are masked")
     print(f"kernel symbols: {len(ka)} in {a}, {len(kb)} in {b}")
     only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
     for s in only_a:
@@ -71,7 +89,7 @@ def compare(a, b, allow):
     print(f"identical bodies: {len(set(ka) & set(kb)) - len(diff)}; differing: {len(diff)} ({len(diff) - len(bad)} permitted)")
     for s in diff:
         print("  differs%s: %s" % ("" if s in bad else " (permitted)", s))
-    return 1 if (bad or only_a or only_b) else 0
+    return 1 if (bad or only_a or [s for s in only_b if not (allow and re.search(allow, s))]) else 0
 
 
 if __name__ == "__main__":
@@ -79,4 +97,4 @@ if __name__ == "__main__":
         emit(sys.argv[2], sys.argv[3])
     else:
         allow = sys.argv[sys.argv.index("--allow") + 1] if "--allow" in sys.argv else None
-        sys.exit(compare(sys.argv[2], sys.argv[3], allow))
+        sys.exit(compare(sys.argv[2], sys.argv[3], allow, "--kernarg" in sys.argv))
