@@ -11,6 +11,7 @@ Two modes:
   * `--synthetic`: seeded image of `--height x --width` (native KITTI 375x1242 by default), timing only -- no dataset on the box.
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
 (:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
+`--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -97,9 +98,31 @@ parser.add_argument('--device-metrics', action='store_true', help='KITTI depth e
                     '(fal_net_amd/metrics.py) into a table read once after the last frame, instead of two full-size copies and float64 numpy per frame')
 
 
+def _sweep_count(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError('--sweep needs at least one view, got {}'.format(n))
+    return n
+
+
+parser.add_argument('--sweep', type=_sweep_count, default=None, metavar='V',
+                    help='also render V views at evenly spaced fractions of the baseline over --sweep-range from each frame\'s logits (fal_net_amd/views.py: one '
+                         'fused launch per 8 views) into Sweep/<frame>_v<view>.png, and the disparity in the right view\'s own frame into r_disp/<frame>.png')
+parser.add_argument('--sweep-range', type=float, nargs=2, default=[-1.0, 1.0], metavar=('LO', 'HI'),
+                    help='first and last baseline fraction of --sweep: 0 is the left camera, 1 the right one; |t| <= 2')
+
+
 def checkpoint_path(a):
     """Test_KITTI.py:119-120: os.path.join(args.dataset, args.time_stamp, args.model + args.details); --checkpoint overrides."""
     return a.checkpoint or os.path.join(a.dataset, a.time_stamp, a.model + a.details)
+
+
+def sweep_fractions(a):
+    """The --sweep baseline fractions: V evenly spaced values from LO to HI (one view: LO), or None without --sweep."""
+    if a.sweep is None:
+        return None
+    lo, hi = a.sweep_range
+    return [lo + (hi - lo) * i / (a.sweep - 1) for i in range(a.sweep)] if a.sweep > 1 else [lo]
 
 
 def refuse_out_of_scope(a):
@@ -140,6 +163,18 @@ def main():
     if args.dump:
         from fal_net_amd import dumps
         writer = dumps.FrameWriter(save_path, args.dump, ply_format=args.ply_format)
+    fractions, sweep_writer = sweep_fractions(args), None
+    if fractions is not None:
+        from fal_net_amd import dumps, views
+        try:
+            views.check_baselines(fractions)
+        except ValueError as e:
+            raise SystemExit('--sweep-range: {}'.format(e))
+        sweep_writer = dumps.SweepWriter(save_path)
+
+    def sweep_line():
+        if sweep_writer is not None:
+            print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
 
     if dataset_mode:
         from fal_net_amd import datasets as DS
@@ -152,12 +187,12 @@ def main():
         loader = DS.make_loader(DS.StereoValDataset(root, triples), 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items()))
+            f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if args.sweep is not None or k not in ('sweep', 'sweep_range')))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
-                                 device_metrics=args.device_metrics)
+                                 device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))
@@ -165,6 +200,7 @@ def main():
         if args.evaluate:  # :282-284
             print('* EPE: {0}'.format(res['epe']))
             print(res['kitti_table'])
+        sweep_line()
         print(json.dumps({'dataset': args.tdataName, 'frames': res['n'], 'dtype': args.dtype, 'post': post, 'epe': res['epe'], 'kitti': res['kitti'],
                           'sec_per_image': res['sec_per_image'], 'errors_txt': os.path.join(save_path, 'errors.txt')}))
         return
@@ -187,6 +223,9 @@ def main():
             times.append(time.time() - t0)
         if writer is not None:  # the one seeded frame, after the timed loop
             inference.dump_frame(writer, 0, pan_model, left, disp, min_disp, max_disp)
+        if sweep_writer is not None:
+            inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
+    sweep_line()
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))
 

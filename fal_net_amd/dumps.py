@@ -231,3 +231,34 @@ class FrameWriter:
                 grey = feature_u8(f)[0].cpu().numpy()
                 for c in range(grey.shape[0]):
                     Image.fromarray(grey[c]).save(self.file("feats", i, layer, c))
+
+
+class SweepWriter:
+    """Writes the views of a baseline sweep (fal_net_amd/views.py) under `save_path`: Sweep/{frame:010d}_v{view:02d}.png through image_u8, and
+    the disparity in the right view's own frame (the t = 1 view) as r_disp/{frame:010d}.png through disparity_png.  Its two folders are its
+    own: FrameWriter, DUMP_KINDS and the reference's five folders do not know about them."""
+    folders = {"sweep": "Sweep", "r_disp": "r_disp"}
+
+    def __init__(self, save_path):
+        self.save_path = save_path
+        self.paths = {k: os.path.join(save_path, d) for k, d in self.folders.items()}
+        for p in self.paths.values():
+            os.makedirs(p, exist_ok=True)
+        self.files = 0
+
+    def file(self, kind, i, view=None):
+        if kind == "sweep":
+            return os.path.join(self.paths[kind], "{:010d}_v{:02d}.png".format(i, view))
+        return os.path.join(self.paths[kind], "{:010d}.png".format(i))
+
+    def write(self, i, views, right_disp=None):
+        """Frame `i` (batch size 1): views (1, V, 3, H, W) normalised images, right_disp (1, 1, H, W) the t = 1 disparity or None."""
+        from PIL import Image
+        assert views.dim() == 5 and views.shape[0] == 1 and views.shape[2] == 3, tuple(views.shape)
+        rgb = image_u8(views[0]).cpu().numpy()  # the V views as one batch: (V, H, W, 3) u8
+        for j in range(rgb.shape[0]):
+            Image.fromarray(rgb[j]).save(self.file("sweep", i, j))
+            self.files += 1
+        if right_disp is not None:
+            Image.fromarray(disparity_png(right_disp)[0].cpu().numpy()).save(self.file("r_disp", i))
+            self.files += 1

@@ -1,7 +1,8 @@
 """Inference post-processing of Test_KITTI.py (ms_pp :287-300, flip post-process :200-203) around the HIP model.
 The resampling of the 1- and 3-channel maps (bilinear x2/3, nearest back) goes through falnet_resize_planar; only the
 host-side 95th percentile stays in numpy exactly as in the reference (opt-in: the exact device-side percentile of dumps.py); the two
-network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter)."""
+network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter), `evaluate(sweep_writer=...)` its views along the
+baseline (dumps.SweepWriter)."""
 import math
 
 import numpy as np
@@ -59,8 +60,20 @@ def dump_frame(writer, i, pan_model, left, disp, min_disp, max_pix):
     writer.write(i, left, disp, pan=pan, feats=feats)
 
 
+def sweep_frame(sweep_writer, i, pan_model, left, min_disp, max_pix, fractions):
+    """Frame `i` through a dumps.SweepWriter: the views at the baseline `fractions` and the disparity in the right view's own frame (t = 1),
+    all from the logits of one more disparity-only forward (views.render)."""
+    from . import views as V
+    ts = list(fractions)
+    if 1.0 not in ts:
+        ts.append(1.0)  # rendered for its disparity only
+    imgs, disps, _ = V.render(pan_model, left, min_disp, max_pix, ts)
+    sweep_writer.write(i, imgs[:, :len(fractions)], right_disp=disps[:, ts.index(1.0)])
+
+
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
-             print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False):
+             print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
+             sweep_fractions=None):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -69,7 +82,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     writer: a dumps.FrameWriter -- every frame's outputs are also written to disk (:211-253), after the timed region and after the metrics;
     where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp.
     device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
-    metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1)."""
+    metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1).
+    sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame)."""
     import time
     from . import datasets as DS
     from . import myUtils as utils
@@ -114,6 +128,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                         kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
                 if writer is not None:
                     dump_frame(writer, n, pan_model, left, disp, mn, mx)
+                if sweep_writer is not None:
+                    sweep_frame(sweep_writer, n, pan_model, left, mn, mx, sweep_fractions)
                 n += 1
             if log is not None and i % print_freq == 0:
                 a1 = kitti.avg[4] if table is None else table.running_mean("a1")

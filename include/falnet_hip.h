@@ -391,6 +391,17 @@ int falnet_med_masks_fwd(const float* dlog0, const float* min_disp, const float*
 int falnet_med_maskr_acfalse_fwd(const float* dlog0, const float* min_disp, const float* max_disp, const float* stats,
                                  float* maskR, int B, int N, int H, int W, void* stream);
 
+/* Views and disparities along the baseline from the logits of one forward (inference only: no gradient, no statistics).  View v shifts
+ * plane n by t[v] * d_n (W-1)/W pixels (2-tap, zero padded on BOTH sides), takes the softmax over the shifted logits and blends the
+ * equally shifted left image; disps is sum_n d_n P_n in the view's own frame, in full-baseline pixels (not scaled by t).  t = 1 is
+ * falnet_med_head_fwd's p_im0 (and the reference's commented-out `dispr`), t = 0 gives back `left` and `disp`, t < 0 renders to the other
+ * side of the left camera.  All planar f32; one launch reads each logit row once for its V views.
+ *   t_host: HOST array of V baseline fractions, 1 <= V <= 8, each finite with |t| <= 2 (passed to the kernel by value)
+ *   views [B][V][3][H][W] (or NULL), disps [B][V][1][H][W] (or NULL); at least one of them.  `left` may be NULL when views is.
+ * Returns non-zero and launches nothing on a refused argument (sizes: those falnet_med_head_fwd accepts). */
+int falnet_med_sweep_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp,
+                         const float* t_host, int V, float* views, float* disps, int B, int N, int H, int W, void* stream);
+
 /* ---- losses (loss_functions.py) ; all write/accumulate a scalar in `out` (f32, device) ---- */
 /* out[0] (+)= scale * sum(mask * |a - b|) ; mask NULL or [B][1][H][W] broadcast over C (loss_functions.py:53) */
 int falnet_l1_fwd(const float* a, const float* b, const float* mask, int B, int C, int64_t HW,
