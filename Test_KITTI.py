@@ -2,7 +2,9 @@
 """Inference / evaluation entry point (reference: Test_KITTI.py) on the MI355X implementation.
 
 Two modes:
-  * dataset mode (`-d <root> -tn Kitti2015`, or `-tn Kitti_eigen_test_improved --test_list <file>`): the reference's evaluation
+  * dataset mode (`-d <root> -tn Kitti2015`, `-tn Kitti_eigen_test_improved --test_list <file>`, or `-tn Kitti_eigen_test_original`, whose
+    ground truth is the reference's `<frame>.npy` beside each image or -- `--velodyne-root <raw KITTI>` -- the frame's Velodyne scan
+    projected on the GPU, fal_net_amd/velodyne.py): the reference's evaluation
     loop (Test_KITTI.py:103-117 file-list dataset at batch size 1, :163-208 forward + flip / multi-scale post-processing,
     :255-271 per-image KITTI depth errors and EPE, :277-280 `errors.txt`) over full-size frames of mixed sizes.  Frames are decoded
     by loader workers (Pillow) and normalised on the GPU; the network, `ms_pp` resampling and flips are HIP kernels; the metric
@@ -43,7 +45,8 @@ def _switch(p, *names, default, help):
 # (the reference's is the author's desktop) and the values are typed.
 parser = argparse.ArgumentParser(description='Testing pan generation (FAL_net on MI355X)', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
 parser.add_argument('-d', '--data', metavar='DIR', default=None, help='path to dataset; frames are read from <data>/<tdataName>')
-parser.add_argument('-tn', '--tdataName', metavar='Test Data Set Name', default='Kitti_eigen_test_improved', choices=['Kitti2015', 'Kitti_eigen_test_improved'])
+parser.add_argument('-tn', '--tdataName', metavar='Test Data Set Name', default='Kitti_eigen_test_improved',
+                    choices=['Kitti2015', 'Kitti_eigen_test_improved', 'Kitti_eigen_test_original'])
 parser.add_argument('-relbase', '--rel_baselne', type=float, default=1, help='Relative baseline of testing dataset')
 parser.add_argument('-mdisp', '--max_disp', type=float, default=300, help='of the training patch W')
 parser.add_argument('-mindisp', '--min_disp', type=float, default=2, help='of the training patch W')
@@ -68,9 +71,17 @@ _switch(parser, '-mspp', '--ms_post_process', default=True, help='Post-processin
 _switch(parser, '-median', '--median', default=False, help='use median scaling (not needed when training from stereo)')
 # additions of this implementation (no reference counterpart)
 parser.add_argument('--checkpoint', default=None, help='checkpoint file given directly instead of composing it from -dt / -ts / -m / -dtl')
-parser.add_argument('--test_list', default=os.path.join('Datasets', 'kitti_eigen_test_improved.txt'),
+DEFAULT_TEST_LIST = os.path.join('Datasets', 'kitti_eigen_test_improved.txt')
+ORIGINAL_TEST_LIST = os.path.join('Datasets', 'kitti_eigen_test_original.txt')
+parser.add_argument('--test_list', default=DEFAULT_TEST_LIST,
                     help="Eigen split: one 'left right [gt]' line per frame, paths relative to <data>/<tdataName> (the reference opens "
-                         "Datasets/kitti_eigen_test_improved.txt relative to the working directory)")
+                         "Datasets/kitti_eigen_test_improved.txt relative to the working directory); with -tn Kitti_eigen_test_original the "
+                         "default becomes Datasets/kitti_eigen_test_original.txt")
+parser.add_argument('--velodyne-root', default=None, metavar='DIR',
+                    help='-tn Kitti_eigen_test_original: the raw KITTI tree (<DIR>/<date>/<drive>/velodyne_points/data/<frame>.bin and <DIR>/<date>/calib_*.txt); '
+                         'every frame\'s ground truth is its Velodyne scan projected on the device (fal_net_amd/velodyne.py).  Default: the reference\'s layout, '
+                         'a ready-made <frame>.npy depth map beside each image (tools/project_velodyne.py writes them)')
+parser.add_argument('--velodyne-cam', type=int, default=2, choices=[2, 3], help='camera the scans are projected into (2: left colour image, 3: right)')
 parser.add_argument('--save-path', default=None, help='where errors.txt / settings.txt go (default Test_Results/<tdataName>/<model>/<time_stamp>[fpp][mspp], :81-85)')
 parser.add_argument('--synthetic', action='store_true', help='timing on a seeded image (default when no --data is given)')
 parser.add_argument('--allow-seeded-weights', action='store_true', help='dataset mode without a checkpoint: evaluate SEEDED (untrained) weights (tests)')
@@ -115,6 +126,13 @@ parser.add_argument('--sweep-range', type=float, nargs=2, default=[-1.0, 1.0], m
 def checkpoint_path(a):
     """Test_KITTI.py:119-120: os.path.join(args.dataset, args.time_stamp, args.model + args.details); --checkpoint overrides."""
     return a.checkpoint or os.path.join(a.dataset, a.time_stamp, a.model + a.details)
+
+
+def resolve_test_list(a):
+    """--test_list; left at its default with -tn Kitti_eigen_test_original it is that split's own list (Kitti_eigen_test_original.py:32)."""
+    if a.tdataName == 'Kitti_eigen_test_original' and a.test_list == DEFAULT_TEST_LIST:
+        return ORIGINAL_TEST_LIST
+    return a.test_list
 
 
 def sweep_fractions(a):
@@ -181,10 +199,15 @@ def main():
         args.batch_size = 1  # kitty mixes image sizes! (:112)
         args.sparse = True  # disparities are sparse (from lidar) (:113)
         root = os.path.join(args.data, args.tdataName)
-        triples = DS.kitti2015_pairs(root) if args.tdataName == 'Kitti2015' else DS.eigen_test_triples(args.test_list, root)
+        if args.tdataName == 'Kitti_eigen_test_original':
+            triples = DS.eigen_original_triples(resolve_test_list(args), root, args.velodyne_root)
+            dataset = DS.StereoEvalDataset(root, triples, cam=args.velodyne_cam)
+        else:
+            triples = DS.kitti2015_pairs(root) if args.tdataName == 'Kitti2015' else DS.eigen_test_triples(args.test_list, root)
+            dataset = DS.StereoValDataset(root, triples)
         if not triples:
             raise SystemExit('no test frame with ground truth found under {}'.format(root))
-        loader = DS.make_loader(DS.StereoValDataset(root, triples), 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
+        loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if args.sweep is not None or k not in ('sweep', 'sweep_range')))

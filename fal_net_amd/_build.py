@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libfalnet_hip.so")
-SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "losses.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
+SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "losses.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "velo.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  The MED head kernels are f32 VALU work per pixel and plane: the SLP vectoriser pairs independent scalar
@@ -21,10 +21,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # dump.hip reproduces the host's f32 arithmetic operation by operation (its 8-bit outputs are compared with numpy byte for byte): a
 # multiply and an add must not contract into one fused multiply-add there.  metrics.hip restates the host's float64 metric chain in the host's
 # order for the same reason (its threshold counts are compared with numpy's as integers).  augment_batch.hip restates the host's float64
-# resampling coefficients (data_transforms.resample_coeffs) for the same reason: its 22-bit integers must equal the host's.
+# resampling coefficients (data_transforms.resample_coeffs) for the same reason: its 22-bit integers must equal the host's.  velo.hip
+# restates the host's float64 projection sums in a fixed order: the pixel a point lands on must be the host's.
 FILE_FLAGS = {"med_head.hip": ["-fno-slp-vectorize"], "med_head2.hip": ["-fno-slp-vectorize"], "med_sweep.hip": ["-fno-slp-vectorize"],
               "dump.hip": ["-ffp-contract=off"],
-              "metrics.hip": ["-ffp-contract=off"], "augment_batch.hip": ["-ffp-contract=off"]}
+              "metrics.hip": ["-ffp-contract=off"], "augment_batch.hip": ["-ffp-contract=off"], "velo.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out, deps):

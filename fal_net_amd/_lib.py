@@ -193,6 +193,7 @@ SIGNATURES = {
     "falnet_depth_errors": [_P, _P, _I, _I, _I, _D, _P, _D, _D, _P, _P, _P],
     "falnet_epe": [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     "falnet_view_errors": [_P, _P, _F, _F, _F, _I, _I, _I, _P, _P, _P],
+    "falnet_velo_project": [_P, _I, _P, _I, _I, _I, _P, _P],
 }
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64}

@@ -9,6 +9,7 @@ a LIST of pairs; it becomes one (B, 3, crop_h, crop_w) tensor after the crop.
 
 Nothing here needs a GPU to import; the augmentation step does (no CPU fallback, like the rest of the path).
 """
+import collections
 import os
 import random
 
@@ -105,6 +106,65 @@ class StereoValDataset(data.Dataset):
         left, right = _imread(os.path.join(self.root, lp)), _imread(os.path.join(self.root, rp))
         disp = None if dp is None else torch.from_numpy(_imread(os.path.join(self.root, dp)).astype(np.float32) / 256.0)
         return torch.from_numpy(left), torch.from_numpy(right), disp
+
+
+VeloRef = collections.namedtuple("VeloRef", ["scan", "calib_dir"])  # ground truth of a triple that is a raw scan: absolute paths
+VeloScan = collections.namedtuple("VeloScan", ["points", "P"])  # what such a frame yields: (N, 4) f32 tensor, 3 x 4 float64 matrix
+
+
+def eigen_original_triples(list_file, root, velodyne_root=None):
+    """The original Eigen test split (Datasets/Kitti_eigen_test_original.py:32-37): every line of `list_file` is 'left right' relative to
+    `root`, e.g. '2011_09_26_drive_0002_sync_02/0000000069.jpg 2011_09_26_drive_0002_sync_03/0000000069.jpg'.  Without `velodyne_root` the
+    ground truth is the reference's ready-made depth map beside the image, '<left minus extension>.npy' under `root`; with it, the frame's raw
+    scan and calibration directory under the raw KITTI tree `velodyne_root` (velodyne.raw_paths) as a VeloRef, projected on the device at
+    evaluation time.  Lines whose image or ground truth is missing are skipped."""
+    from . import velodyne
+    if not os.path.isfile(list_file):
+        raise FileNotFoundError(f"test list {list_file!r} not found (one 'left right' line per frame, paths relative to <data>/<tdataName>).  "
+                                "The original Eigen test split (697 lines) ships with the reference repository as Datasets/kitti_eigen_test_original.txt "
+                                "(github.com/JuanLuisGonzalez/FAL_net); it is not redistributed here: copy it or pass --test_list <file>.")
+    out = []
+    with open(list_file) as f:
+        for ln in f.read().splitlines():
+            c = ln.split()
+            if len(c) < 2 or not os.path.isfile(os.path.join(root, c[0])):
+                continue
+            if velodyne_root is None:
+                gt = os.path.splitext(c[0])[0] + ".npy"
+                if os.path.isfile(os.path.join(root, gt)):
+                    out.append((c[0], c[1], gt))
+            else:
+                scan, calib = velodyne.raw_paths(c[0], velodyne_root)
+                if (os.path.isfile(scan) and os.path.isfile(os.path.join(calib, "calib_cam_to_cam.txt"))
+                        and os.path.isfile(os.path.join(calib, "calib_velo_to_cam.txt"))):
+                    out.append((c[0], c[1], VeloRef(scan, calib)))
+    return out
+
+
+class StereoEvalDataset(StereoValDataset):
+    """StereoValDataset plus the two ground-truth kinds of the original Eigen split (eigen_original_triples), chosen per triple: a '.npy' path
+    loads as the depth map it holds (float32, NOT divided by 256: listdataset_test.py:49-51); a VeloRef yields VeloScan(points, P), the raw scan
+    and the projection matrix of camera `cam`, for inference.evaluate to project at the left image's size.  A calibration directory is parsed once
+    (per loader worker), not once per frame.  Every other triple is StereoValDataset's, unchanged."""
+
+    def __init__(self, root, triples, cam=2):
+        super().__init__(root, triples)
+        self.cam = int(cam)
+        self._P = {}
+
+    def __getitem__(self, index):
+        lp, rp, dp = self.triples[index]
+        if isinstance(dp, VeloRef):
+            from . import velodyne
+            if dp.calib_dir not in self._P:
+                self._P[dp.calib_dir] = velodyne.projection_matrix(dp.calib_dir, self.cam)
+            gt = VeloScan(torch.from_numpy(velodyne.load_scan(dp.scan)), self._P[dp.calib_dir])
+        elif isinstance(dp, str) and dp.endswith(".npy"):
+            gt = torch.from_numpy(np.load(os.path.join(self.root, dp)).astype(np.float32))
+        else:
+            return super().__getitem__(index)
+        left, right = _imread(os.path.join(self.root, lp)), _imread(os.path.join(self.root, rp))
+        return torch.from_numpy(left), torch.from_numpy(right), gt
 
 
 def _list_collate(batch):

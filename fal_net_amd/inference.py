@@ -78,7 +78,9 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
     datasets.StereoValDataset; gt is a disparity map (Kitti2015) or a depth map (Eigen split, listdataset_test.py:43-46 reads both
-    as uint16 / 256).  Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}.
+    as uint16 / 256); with datasets.StereoEvalDataset it may also be the depth map of a '.npy' file or a datasets.VeloScan (a raw Velodyne
+    scan and its projection matrix: the depth map is then velodyne.project of it on the device) -- the original Eigen split.
+    Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}.
     writer: a dumps.FrameWriter -- every frame's outputs are also written to disk (:211-253), after the timed region and after the metrics;
     where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp.
     device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
@@ -112,6 +114,9 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                 torch.cuda.synchronize()
                 batch_time.update(time.time() - t0, 1)
                 if gt is not None and with_metrics:  # `-eval False`: forward and timing only (:255)
+                    if isinstance(gt, DS.VeloScan):  # original Eigen split from a raw scan: the ground truth is projected here, at the left image's size
+                        from . import velodyne
+                        gt = velodyne.project(gt.points.to(dev), gt.P, left_u8.shape[0], left_u8.shape[1])
                     target = gt.to(dev).view(1, 1, *gt.shape)
                     if table is not None:
                         row = table.row(table.n)

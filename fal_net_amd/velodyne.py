@@ -1,0 +1,97 @@
+"""Velodyne ground truth of the original Eigen test split (reference: Datasets/Kitti_eigen_test_original.py, which reads a ready-made
+`<frame>.npy` depth map beside each image and leaves making it to Monodepth's `generate_depth_map`): the raw-KITTI file handling on the host --
+calibration files, the projection matrix, the scan, the paths of a list line -- and the projection itself on the device (csrc/velo.hip:
+falnet_velo_project).
+
+The projection's result is defined operation by operation (include/falnet_hip.h); the host restatement it is tested against is
+tests/_velo_ref.py.  Nothing here needs a GPU to import; `project` does: like the rest of the package it has no CPU fallback and raises on a CPU
+tensor."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+
+def read_calib_file(path):
+    """KITTI's calibration text ('key: v v v ...' per line) -> {key: float64 array}.  Lines whose values do not parse as numbers (calib_time: a
+    date) are skipped, as Monodepth's reader skips them."""
+    out = {}
+    with open(path) as f:
+        for line in f:
+            if ":" not in line:
+                continue
+            key, value = line.split(":", 1)
+            try:
+                out[key.strip()] = np.array([float(v) for v in value.split()], dtype=np.float64)
+            except ValueError:
+                pass
+    return out
+
+
+def projection_matrix(calib_dir, cam=2):
+    """The 3 x 4 float64 matrix that takes a homogeneous Velodyne point to the image plane of camera `cam` (2: left colour, 3: right colour):
+    P_rect_0<cam> . [R_rect_00 | 0; 0 1] . [R T; 0 0 0 1] from calib_cam_to_cam.txt and calib_velo_to_cam.txt, as two float64 np.dot's in
+    Monodepth's order."""
+    if int(cam) not in (2, 3):
+        raise ValueError("cam must be 2 or 3, got {!r}".format(cam))
+    cam2cam = read_calib_file(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
+    velo2cam = read_calib_file(os.path.join(calib_dir, "calib_velo_to_cam.txt"))
+    for name, d, keys in (("calib_cam_to_cam.txt", cam2cam, ("R_rect_00", "P_rect_0%d" % int(cam))), ("calib_velo_to_cam.txt", velo2cam, ("R", "T"))):
+        for k in keys:
+            if k not in d:
+                raise KeyError("{} has no numeric entry {!r}".format(os.path.join(calib_dir, name), k))
+    v2c = np.hstack((velo2cam["R"].reshape(3, 3), velo2cam["T"].reshape(3, 1)))
+    v2c = np.vstack((v2c, np.array([0.0, 0.0, 0.0, 1.0])))
+    r_rect = np.eye(4)
+    r_rect[:3, :3] = cam2cam["R_rect_00"].reshape(3, 3)
+    p_rect = cam2cam["P_rect_0%d" % int(cam)].reshape(3, 4)
+    return np.dot(np.dot(p_rect, r_rect), v2c)
+
+
+def load_scan(path):
+    """A raw scan (velodyne_points/data/<frame>.bin) as an (N, 4) float32 array: x forward, y left, z up, reflectance."""
+    size = os.path.getsize(path)
+    if size % 16:
+        raise ValueError("{}: {} bytes is not a whole number of 16-byte points (x, y, z, reflectance as float32): the file is truncated "
+                         "or is not a Velodyne scan".format(path, size))
+    return np.fromfile(path, np.float32).reshape(-1, 4)
+
+
+def raw_paths(left_rel, raw_root):
+    """A left-image entry of the reference's list, '<date>_drive_<n>_sync_02/<frame>.jpg' -> (the scan
+    <raw_root>/<date>/<date>_drive_<n>_sync/velodyne_points/data/<frame>.bin, the calibration directory <raw_root>/<date>) of the raw KITTI tree."""
+    folder, name = os.path.split(left_rel.replace("\\", "/"))
+    folder = os.path.basename(folder)
+    frame = os.path.splitext(name)[0]
+    if not folder.endswith(("_sync_02", "_sync_03")) or len(folder) < 19 or not frame:
+        raise ValueError("{!r} is not '<date>_drive_<n>_sync_0<cam>/<frame>.<ext>'".format(left_rel))
+    drive, date = folder[:-3], folder[:10]
+    return os.path.join(raw_root, date, drive, "velodyne_points", "data", frame + ".bin"), os.path.join(raw_root, date)
+
+
+def project(points, P, H, W, vel_depth=False, out=None):
+    """The scan `points` (CUDA f32 (N, 4): x, y, z, reflectance) through the 3 x 4 float64 matrix `P` into an (H, W) f32 depth map on the same
+    device: per pixel the depth of the closest point that lands on it, 0 where none does (falnet_velo_project).  vel_depth: a point's depth is its
+    x instead of its camera z.  out: an (H, W) f32 CUDA tensor to write into (every pixel is written).  Bit-identical for any order of the points."""
+    from . import _lib as L
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise RuntimeError("fal_net_amd.velodyne.project runs on an MI355X only (no CPU fallback); points is {}".format(
+            "on " + str(points.device) if torch.is_tensor(points) else type(points).__name__))
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError("points: expected an (N, 4) float32 tensor, got {} {}".format(tuple(points.shape), points.dtype))
+    Pm = np.ascontiguousarray(np.asarray(P, dtype=np.float64))
+    if Pm.shape != (3, 4):
+        raise ValueError("P: expected a 3 x 4 matrix, got shape {}".format(Pm.shape))
+    H, W = int(H), int(W)
+    points = points.detach().contiguous()
+    if out is None:
+        out = torch.empty((max(H, 0), max(W, 0)), dtype=torch.float32, device=points.device)
+    elif (not torch.is_tensor(out) or out.device != points.device or out.dtype != torch.float32 or tuple(out.shape) != (H, W)
+          or not out.is_contiguous()):
+        raise ValueError("out: expected a contiguous ({}, {}) float32 tensor on {}".format(H, W, points.device))
+    p12 = (C.c_double * 12)(*Pm.reshape(-1).tolist())
+    with torch.cuda.device(points.device):
+        L.check(L.lib().falnet_velo_project(L.ptr(points), int(points.shape[0]), p12, H, W, int(bool(vel_depth)), L.ptr(out), L.stream_ptr()),
+                "velo_project")
+    return out

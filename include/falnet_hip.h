@@ -654,6 +654,16 @@ int falnet_epe(const float* pred, int h, int w, const float* target, int B, int 
 int falnet_view_errors(const float* out, const float* label, float mean_r, float mean_g, float mean_b, int B, int H, int W, double* row, void* workspace,
                        void* stream);
 
+/* ---- Velodyne ground truth (csrc/velo.hip; the original Eigen split, Datasets/Kitti_eigen_test_original.py) -----------------------------------
+ * Monodepth's generate_depth_map of one raw KITTI scan on the device.  points: n_points x 4 f32 (x, y, z, reflectance) as the .bin file holds them,
+ * on the device; the fourth value is ignored and taken as 1.  P: 12 doubles on the HOST, the row-major 3 x 4 velodyne-to-image matrix, passed on to
+ * the kernel by value.  Per point with x >= 0: s_i = ((P[i][0] x + P[i][1] y) + P[i][2] z) + P[i][3] in f64 with no fused multiply-add,
+ * u = rint(s_0 / s_2) - 1, v = rint(s_1 / s_2) - 1 (half to even), depth = (float)s_2 (vel_depth: x); it lands on (v, u) when 0 <= u < W and
+ * 0 <= v < H as doubles.  depth_out (H x W f32, device, every pixel written): the minimum depth over the points on the pixel through an integer
+ * atomicMin on the monotone image of the f32 -- bit-identical for any order of the points and from run to run, no floating-point atomics; 0 where
+ * no point lands and where the minimum is negative.  n_points = 0 gives an all-zero map.  H W < 2^31; every entry of P finite.  Not replayable. */
+int falnet_velo_project(const float* points, int n_points, const double* P, int H, int W, int vel_depth, float* depth_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,196 @@
+"""CPU: the host side of the original Eigen split -- the definition of the Velodyne projection (tests/_velo_ref.py: spec) against Monodepth's
+original formulation (monodepth_host), the raw-KITTI file handling of fal_net_amd/velodyne.py, the two ground-truth layouts of
+datasets.eigen_original_triples / StereoEvalDataset, and the command line.  No GPU."""
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import _velo_ref as R
+from fal_net_amd import datasets as DS
+from fal_net_amd import velodyne
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+# ---- the definition equals the original formulation ----------------------------------------------------------------------------------------------
+# The two differ in the order of the four-term sums (spec: fixed; np.dot: whatever the BLAS does) and in how the minimum is found.  Equality is
+# exact, with no tolerance: should a seed ever differ, the cause is the BLAS's summation order moving one point across a rounding boundary, not the
+# definition -- choose another seed and say so here.
+@pytest.mark.parametrize("seed,H,W,n,scale", [(0, 375, 1242, 120000, 1.0), (2, 375, 1242, 120000, 1.0), (1, 37, 124, 5000, 0.1)],
+                         ids=["seed0-375x1242", "seed2-375x1242", "seed1-37x124"])
+def test_spec_equals_monodepth_host(seed, H, W, n, scale):
+    P, pts = R.kitti_like_P(scale), R.seeded_scan(seed, n)
+    a, b = R.spec(P, pts, H, W), R.monodepth_host(P, pts, H, W)
+    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape == (H, W)
+    x, y, z = (pts[pts[:, 0] >= 0, i].astype(np.float64) for i in range(3))
+    s = [P[i, 0] * x + P[i, 1] * y + P[i, 2] * z + P[i, 3] for i in range(3)]
+    u, v = np.rint(s[0] / s[2]) - 1, np.rint(s[1] / s[2]) - 1
+    landed = int(((u >= 0) & (v >= 0) & (u < W) & (v < H)).sum())
+    print(f"seed {seed} {H}x{W}: {landed} points land on {int((a > 0).sum())} pixels; {int((a != b).sum())} pixels differ")
+    assert landed > 1.2 * (a > 0).sum() > 0  # collisions are plentiful
+    assert np.array_equal(a, b)
+
+
+def test_spec_equals_monodepth_host_vel_depth():
+    P, pts = R.kitti_like_P(0.1), R.seeded_scan(1, 5000)
+    a = R.spec(P, pts, 37, 124, vel_depth=True)
+    assert np.array_equal(a, R.monodepth_host(P, pts, 37, 124, vel_depth=True)) and not np.array_equal(a, R.spec(P, pts, 37, 124))
+
+
+def test_spec_rules_on_crafted_points():
+    P = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 0, 1.0]])  # s_2 = 1: u = rint(x) - 1, v = rint(y) - 1, depth 1
+    pts = np.array([[2.5, 1, 0, 0], [3.5, 1, 0, 0], [-0.25, 1, 0, 0], [np.nan, 1, 0, 0]], np.float32)
+    m = R.spec(P, pts, 4, 6)
+    assert m[0, 1] == 1 and m[0, 3] == 1 and m.sum() == 2  # 2.5 -> 2, 3.5 -> 4 (half to even), then minus one; x < 0 and NaN dropped
+    Pz = np.array([[0, 1.0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 0]])  # s_2 = z, u = v = rint(y / z) - 1
+    both = np.array([[1, -4, -2, 0], [1, 6, 3, 0]], np.float32)  # depth -2 and depth 3 on pixel (1, 1)
+    for order in (both, both[::-1]):
+        assert R.spec(Pz, order, 3, 3)[1, 1] == 0 and R.monodepth_host(Pz, order, 3, 3)[1, 1] == 0
+
+
+# ---- calibration files ----------------------------------------------------------------------------------------------------------------------------
+def test_read_calib_file_and_projection_matrix(tmp_path):
+    d = str(tmp_path / "2011_09_26")
+    R.write_calib(d)
+    c = velodyne.read_calib_file(os.path.join(d, "calib_cam_to_cam.txt"))
+    assert "calib_time" not in c and set(c) == {"corner_dist", "S_00", "R_rect_00", "P_rect_02", "P_rect_03"}
+    assert c["R_rect_00"].dtype == np.float64 and np.array_equal(c["R_rect_00"], R.R_RECT_00.reshape(-1)) and np.array_equal(c["S_00"], [1392.0, 512.0])
+    P2, P3 = velodyne.projection_matrix(d), velodyne.projection_matrix(d, cam=3)
+    assert P2.shape == (3, 4) and P2.dtype == np.float64
+    assert np.array_equal(P2, R.compose_P()) and np.array_equal(P3, R.compose_P(R.P_RECT_03)) and not np.array_equal(P2, P3)
+    with pytest.raises(ValueError):
+        velodyne.projection_matrix(d, cam=1)
+    R.write_calib(str(tmp_path / "no3"), cam3=False)
+    with pytest.raises(KeyError, match="P_rect_03"):
+        velodyne.projection_matrix(str(tmp_path / "no3"), cam=3)
+
+
+# ---- paths and scans ------------------------------------------------------------------------------------------------------------------------------
+def test_raw_paths_on_the_head_of_the_reference_list(golden_dir):
+    lines = open(os.path.join(golden_dir, "eigen_original_head.txt")).read().splitlines()
+    assert len(lines) == 8
+    for ln in lines:
+        left = ln.split()[0]
+        m = re.fullmatch(r"(\d{4}_\d\d_\d\d)_drive_(\d{4})_sync_02/(\d{10})\.jpg", left)
+        assert m, left
+        scan, calib = velodyne.raw_paths(left, "/raw")
+        assert scan == f"/raw/{m.group(1)}/{m.group(1)}_drive_{m.group(2)}_sync/velodyne_points/data/{m.group(3)}.bin"
+        assert calib == f"/raw/{m.group(1)}"
+    assert velodyne.raw_paths(lines[0].split()[0], "/raw")[0] == "/raw/2011_09_26/2011_09_26_drive_0002_sync/velodyne_points/data/0000000069.bin"
+    with pytest.raises(ValueError):
+        velodyne.raw_paths("training/image_2/000000_10.png", "/raw")
+
+
+def test_load_scan_and_its_error_on_a_truncated_file(tmp_path):
+    pts = R.seeded_scan(3, 10)
+    pts.tofile(tmp_path / "ok.bin")
+    got = velodyne.load_scan(str(tmp_path / "ok.bin"))
+    assert got.dtype == np.float32 and got.shape == (10, 4) and np.array_equal(got, pts)
+    with open(tmp_path / "cut.bin", "wb") as f:
+        f.write(pts.tobytes()[:-6])
+    with pytest.raises(ValueError, match="16-byte"):
+        velodyne.load_scan(str(tmp_path / "cut.bin"))
+
+
+def test_project_has_no_cpu_fallback():
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        velodyne.project(torch.zeros(3, 4), R.kitti_like_P(), 4, 4)
+
+
+# ---- the two layouts --------------------------------------------------------------------------------------------------------------------------------
+def fake_tree(tmp_path, H=12, W=20):
+    """root: two frames of the list's layout (the second without a .npy); raw: scans for frames 0 and 1, calibration; a third list line has no image."""
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    root, raw = tmp_path / "Kitti_eigen_test_original", tmp_path / "raw"
+    drive = "2011_09_26_drive_0002_sync"
+    lines = []
+    for i in range(3):
+        lines.append(f"{drive}_02/{i:010d}.jpg {drive}_03/{i:010d}.jpg")
+        if i == 2:
+            continue
+        for cam in ("_02", "_03"):
+            os.makedirs(root / (drive + cam), exist_ok=True)
+            Image.fromarray(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)).save(root / (drive + cam) / f"{i:010d}.jpg")
+        os.makedirs(raw / "2011_09_26" / drive / "velodyne_points" / "data", exist_ok=True)
+        R.seeded_scan(i, 50).tofile(raw / "2011_09_26" / drive / "velodyne_points" / "data" / f"{i:010d}.bin")
+    depth = (rng.random((H, W)) * 80).astype(np.float64)  # a float64 file: it comes back as float32, unscaled
+    np.save(root / (drive + "_02") / f"{0:010d}.npy", depth)
+    R.write_calib(str(raw / "2011_09_26"))
+    lst = tmp_path / "list.txt"
+    lst.write_text("\n".join(lines) + "\n")
+    return str(root), str(raw), str(lst), depth
+
+
+def test_eigen_original_triples_both_layouts(tmp_path):
+    root, raw, lst, depth = fake_tree(tmp_path)
+    drive = "2011_09_26_drive_0002_sync"
+    npy = DS.eigen_original_triples(lst, root)
+    assert npy == [(f"{drive}_02/0000000000.jpg", f"{drive}_03/0000000000.jpg", f"{drive}_02/0000000000.npy")]  # frame 1 has no .npy, frame 2 no image
+    left, right, gt = DS.StereoEvalDataset(root, npy)[0]
+    assert left.dtype == torch.uint8 and tuple(left.shape) == (12, 20, 3) and tuple(right.shape) == (12, 20, 3)
+    assert gt.dtype == torch.float32 and torch.equal(gt, torch.from_numpy(depth.astype(np.float32)))  # no division by 256
+    scans = DS.eigen_original_triples(lst, root, velodyne_root=raw)
+    assert [t[0] for t in scans] == [f"{drive}_02/{i:010d}.jpg" for i in range(2)]
+    assert all(isinstance(t[2], DS.VeloRef) and t[2].calib_dir == os.path.join(raw, "2011_09_26") for t in scans)
+    ds = DS.StereoEvalDataset(root, scans)
+    g0, g1 = ds[0][2], ds[1][2]
+    assert isinstance(g0, DS.VeloScan) and g0.points.dtype == torch.float32 and tuple(g0.points.shape) == (50, 4)
+    assert np.array_equal(g0.points.numpy(), R.seeded_scan(0, 50)) and np.array_equal(g1.points.numpy(), R.seeded_scan(1, 50))
+    assert g0.P.dtype == np.float64 and np.array_equal(g0.P, R.compose_P()) and g1.P is g0.P  # the calibration directory is parsed once
+    assert np.array_equal(DS.StereoEvalDataset(root, scans, cam=3)[0][2].P, R.compose_P(R.P_RECT_03))
+    # the loader carries a scan through its collate (and pinning, where there is a device) unchanged
+    batch = next(iter(DS.make_loader(DS.StereoEvalDataset(root, scans[:1]), 1, 0, shuffle=False, drop_last=False)))
+    assert isinstance(batch[0][2], DS.VeloScan) and torch.equal(batch[0][2].points, g0.points)
+    os.remove(os.path.join(raw, "2011_09_26", "calib_velo_to_cam.txt"))
+    assert DS.eigen_original_triples(lst, root, velodyne_root=raw) == []
+    with pytest.raises(FileNotFoundError, match="kitti_eigen_test_original.txt"):
+        DS.eigen_original_triples(str(tmp_path / "missing.txt"), root)
+
+
+def test_png_triple_is_what_it_was(tmp_path):
+    """A PNG ground truth through the new class, through the old one, and through the old one's arithmetic restated: the same bytes."""
+    from PIL import Image
+    rng = np.random.default_rng(1)
+    for name in ("l.png", "r.png"):
+        Image.fromarray(rng.integers(0, 256, (9, 14, 3), dtype=np.uint8)).save(tmp_path / name)
+    disp = (rng.random((9, 14)) * 80 * 256).astype(np.uint16)
+    Image.fromarray(disp).save(tmp_path / "d.png")
+    triples = [("l.png", "r.png", "d.png"), ("l.png", "r.png", None)]
+    new, old = DS.StereoEvalDataset(str(tmp_path), triples), DS.StereoValDataset(str(tmp_path), triples)
+    for a, b in zip(new[0], old[0]):
+        assert a.dtype == b.dtype and a.numpy().tobytes() == b.numpy().tobytes()
+    assert new[0][2].numpy().tobytes() == (disp.astype(np.float32) / 256.0).tobytes()
+    assert new[1][2] is None and old[1][2] is None
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------------------------------
+def test_parser_accepts_the_original_split(monkeypatch):
+    monkeypatch.syspath_prepend(ROOT)
+    mod = importlib.import_module("Test_KITTI")
+    a = mod.parser.parse_args([])
+    assert a.tdataName == "Kitti_eigen_test_improved" and a.velodyne_root is None and a.velodyne_cam == 2
+    assert mod.resolve_test_list(a) == os.path.join("Datasets", "kitti_eigen_test_improved.txt")
+    a = mod.parser.parse_args(["-tn", "Kitti_eigen_test_original"])
+    assert a.tdataName == "Kitti_eigen_test_original" and mod.resolve_test_list(a) == os.path.join("Datasets", "kitti_eigen_test_original.txt")
+    a = mod.parser.parse_args(["-tn", "Kitti_eigen_test_original", "--velodyne-root", "/raw", "--velodyne-cam", "3", "--test_list", "mine.txt"])
+    assert a.velodyne_root == "/raw" and a.velodyne_cam == 3 and mod.resolve_test_list(a) == "mine.txt"
+    with pytest.raises(SystemExit):
+        mod.parser.parse_args(["--velodyne-cam", "1"])
+    with pytest.raises(SystemExit):
+        mod.parser.parse_args(["-tn", "Kitti_eigen_test_other"])
+
+
+def test_entry_point_in_header_binding_and_build():
+    from fal_net_amd import _build, _lib, ops
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "falnet_hip.h")).read(), flags=re.S)
+    assert re.search(r"\bfalnet_velo_project\s*\(", hdr)
+    sig = _lib.SIGNATURES["falnet_velo_project"]
+    assert len(sig) == 8 and sig[-1] is _lib._P and sig[1] is _lib._I
+    assert "velo.hip" in _build.SOURCES and _build.FILE_FLAGS["velo.hip"] == ["-ffp-contract=off"]
+    assert "velo.hip" not in ops._TUNE_SOURCES and _lib.EXPECTED_VERSION == 600  # the packaged autotune cache stays valid
+    assert "velo_key" in open(os.path.join(_build.CSRC, "velo.hip")).read() and "velo" not in open(os.path.join(_build.CSRC, "dump.hip")).read()
