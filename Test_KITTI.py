@@ -14,6 +14,8 @@ Two modes:
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
 (:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
 `--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
+`--stats KINDS` adds maps of the per-pixel disparity distribution (spread, entropy, arg-max plane, peak mass, peak disparity),
+`--pc-min-conf C` keeps only the confident vertices of the point cloud and `--disparity peak` evaluates the peak disparity, fal_net_amd/confidence.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -123,6 +125,43 @@ parser.add_argument('--sweep-range', type=float, nargs=2, default=[-1.0, 1.0], m
                     help='first and last baseline fraction of --sweep: 0 is the left camera, 1 the right one; |t| <= 2')
 
 
+STATS_KINDS = ('std', 'entropy', 'arg', 'conf', 'peak')
+
+
+def _stats_kinds(v):
+    kinds = [k for k in v.split(',') if k]
+    bad = [k for k in kinds if k not in STATS_KINDS]
+    if bad or not kinds or len(set(kinds)) != len(kinds):
+        raise argparse.ArgumentTypeError('--stats takes a comma-separated subset of {} (each once), got {!r}'.format(','.join(STATS_KINDS), v))
+    return kinds
+
+
+def _min_conf(v):
+    c = float(v)
+    if not 0.0 < c <= 1.0:
+        raise argparse.ArgumentTypeError('--pc-min-conf needs 0 < C <= 1, got {}'.format(v))
+    return c
+
+
+parser.add_argument('--stats', type=_stats_kinds, default=None, metavar='KINDS',
+                    help='comma-separated subset of std,entropy,arg,conf,peak: per-pixel statistics of each frame\'s distribution over the disparity planes '
+                         '(fal_net_amd/confidence.py: one fused launch over the logits) as stats/<frame>_<kind>.png, and one JSON line with their means')
+parser.add_argument('--pc-min-conf', type=_min_conf, default=None, metavar='C',
+                    help='with --dump pc: Point_cloud/<frame>.ply holds only the vertices whose probability mass around the arg-max plane (conf) is at least C')
+parser.add_argument('--disparity', default='mean', choices=['mean', 'peak'],
+                    help='the disparity that is evaluated and dumped: the expectation over all planes, or the expectation over the arg-max plane and its '
+                         'two neighbours of the same forward (only with -mspp False -fpp False)')
+
+
+def check_confidence_args(a):
+    """What the confidence switches need of the others; SystemExit names what is missing."""
+    if a.pc_min_conf is not None and 'pc' not in a.dump:
+        raise SystemExit('--pc-min-conf filters the point cloud of --dump pc: add pc to --dump')
+    if a.disparity == 'peak' and (a.f_post_process or a.ms_post_process):
+        raise SystemExit('--disparity peak is valid only with both post-processing modes off (-mspp False -fpp False): ms_pp and the flip '
+                         'post-processing blend two expectation maps and are not redefined for the peak disparity')
+
+
 def checkpoint_path(a):
     """Test_KITTI.py:119-120: os.path.join(args.dataset, args.time_stamp, args.model + args.details); --checkpoint overrides."""
     return a.checkpoint or os.path.join(a.dataset, a.time_stamp, a.model + a.details)
@@ -159,6 +198,7 @@ def main():
     dtype = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[args.dtype]
     post = 'flip' if args.f_post_process else ('ms_pp' if args.ms_post_process else 'none')
     refuse_out_of_scope(args)
+    check_confidence_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     model_dir = checkpoint_path(args)  # :119-120
     have_ckpt = os.path.isfile(model_dir)
@@ -180,7 +220,8 @@ def main():
     writer = None
     if args.dump:
         from fal_net_amd import dumps
-        writer = dumps.FrameWriter(save_path, args.dump, ply_format=args.ply_format)
+        # with --pc-min-conf the point cloud is the stats writer's: the frame writer keeps the other kinds
+        writer = dumps.FrameWriter(save_path, [k for k in args.dump if k != 'pc' or args.pc_min_conf is None], ply_format=args.ply_format)
     fractions, sweep_writer = sweep_fractions(args), None
     if fractions is not None:
         from fal_net_amd import dumps, views
@@ -190,9 +231,16 @@ def main():
             raise SystemExit('--sweep-range: {}'.format(e))
         sweep_writer = dumps.SweepWriter(save_path)
 
-    def sweep_line():
+    stats_writer = None
+    if args.stats is not None or args.pc_min_conf is not None:
+        from fal_net_amd import confidence
+        stats_writer = confidence.StatsWriter(save_path, args.stats or (), pc_min_conf=args.pc_min_conf, ply_format=args.ply_format)
+
+    def extra_lines():
         if sweep_writer is not None:
             print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
+        if stats_writer is not None:
+            print(json.dumps({'stats': stats_writer.summary()}))
 
     if dataset_mode:
         from fal_net_amd import datasets as DS
@@ -210,12 +258,15 @@ def main():
         loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if args.sweep is not None or k not in ('sweep', 'sweep_range')))
+            hidden = (() if args.sweep is not None else ('sweep', 'sweep_range')) + (() if stats_writer is not None or args.disparity != 'mean' else
+                                                                                  ('stats', 'pc_min_conf', 'disparity'))
+            f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
-                                 device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions)
+                                 device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
+                                 disparity=args.disparity)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))
@@ -223,7 +274,7 @@ def main():
         if args.evaluate:  # :282-284
             print('* EPE: {0}'.format(res['epe']))
             print(res['kitti_table'])
-        sweep_line()
+        extra_lines()
         print(json.dumps({'dataset': args.tdataName, 'frames': res['n'], 'dtype': args.dtype, 'post': post, 'epe': res['epe'], 'kitti': res['kitti'],
                           'sec_per_image': res['sec_per_image'], 'errors_txt': os.path.join(save_path, 'errors.txt')}))
         return
@@ -237,7 +288,10 @@ def main():
         for _ in range(args.iters):
             torch.cuda.synchronize()
             t0 = time.time()
-            disp = pan_model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)  # :196
+            if args.disparity == 'peak':
+                disp = inference.peak_disparity(pan_model, left, min_disp, max_disp)
+            else:
+                disp = pan_model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)  # :196
             if args.f_post_process:
                 disp = inference.flip_post_process(left, pan_model, disp, min_disp, max_disp)
             elif args.ms_post_process:
@@ -248,7 +302,9 @@ def main():
             inference.dump_frame(writer, 0, pan_model, left, disp, min_disp, max_disp)
         if sweep_writer is not None:
             inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
-    sweep_line()
+        if stats_writer is not None:
+            inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
+    extra_lines()
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))
 

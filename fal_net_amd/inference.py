@@ -2,7 +2,8 @@
 The resampling of the 1- and 3-channel maps (bilinear x2/3, nearest back) goes through falnet_resize_planar; only the
 host-side 95th percentile stays in numpy exactly as in the reference (opt-in: the exact device-side percentile of dumps.py); the two
 network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter), `evaluate(sweep_writer=...)` its views along the
-baseline (dumps.SweepWriter)."""
+baseline (dumps.SweepWriter), `evaluate(stats_writer=...)` the statistics of its disparity distribution and its confidence-filtered point cloud
+(confidence.StatsWriter); `evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
 import math
 
 import numpy as np
@@ -71,9 +72,25 @@ def sweep_frame(sweep_writer, i, pan_model, left, min_disp, max_pix, fractions):
     sweep_writer.write(i, imgs[:, :len(fractions)], right_disp=disps[:, ts.index(1.0)])
 
 
+def stats_frame(stats_writer, i, pan_model, left, disp, min_disp, max_pix):
+    """Frame `i` through a confidence.StatsWriter: the statistics of the logits of one more disparity-only forward (confidence.from_model);
+    the filtered point cloud is made of `disp`, the disparity the run evaluates."""
+    from . import confidence
+    st, _ = confidence.from_model(pan_model, left, min_disp, max_pix, stats_writer.which)
+    B, _, H, W = left.shape
+    stats_writer.write(i, left, disp, st, pan_model._plan(B, H, W, left.device).buf["dlog0"].shape[1])
+
+
+def peak_disparity(pan_model, left, min_disp, max_pix):
+    """The forward with the peak disparity (confidence.py: the expectation over the arg-max plane and its two neighbours) in the place of
+    the expectation over all planes: one disparity-only forward and one statistics launch over its logits."""
+    from . import confidence
+    return confidence.from_model(pan_model, left, min_disp, max_pix, ("peak",))[0]["peak"]
+
+
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
-             sweep_fractions=None):
+             sweep_fractions=None, stats_writer=None, disparity="mean"):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -85,7 +102,13 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp.
     device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
     metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1).
-    sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame)."""
+    sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame).
+    stats_writer: a confidence.StatsWriter -- every frame's distribution statistics and its confidence-filtered point cloud are written too (stats_frame).
+    disparity: "mean" (the forward's expectation) or "peak" (peak_disparity; only with post == "none": ms_pp and the flip blend two expectations)."""
+    if disparity not in ("mean", "peak"):
+        raise ValueError("disparity must be 'mean' or 'peak', got {!r}".format(disparity))
+    if disparity == "peak" and post != "none":
+        raise ValueError("disparity='peak' needs post='none': ms_pp and the flip post-processing blend two expectation maps")
     import time
     from . import datasets as DS
     from . import myUtils as utils
@@ -106,7 +129,10 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                 mn = mx * min_disp / max_disp
                 torch.cuda.synchronize()
                 t0 = time.time()
-                disp = pan_model(left, mn, mx, ret_disp=True, ret_subocc=False, ret_pan=False)  # :196
+                if disparity == "peak":
+                    disp = peak_disparity(pan_model, left, mn, mx)
+                else:
+                    disp = pan_model(left, mn, mx, ret_disp=True, ret_subocc=False, ret_pan=False)  # :196
                 if post == "flip":
                     disp = flip_post_process(left, pan_model, disp, mn, mx)
                 elif post == "ms_pp":
@@ -135,6 +161,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                     dump_frame(writer, n, pan_model, left, disp, mn, mx)
                 if sweep_writer is not None:
                     sweep_frame(sweep_writer, n, pan_model, left, mn, mx, sweep_fractions)
+                if stats_writer is not None:
+                    stats_frame(stats_writer, n, pan_model, left, disp, mn, mx)
                 n += 1
             if log is not None and i % print_freq == 0:
                 a1 = kitti.avg[4] if table is None else table.running_mean("a1")

@@ -402,6 +402,37 @@ int falnet_med_maskr_acfalse_fwd(const float* dlog0, const float* min_disp, cons
 int falnet_med_sweep_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp,
                          const float* t_host, int V, float* views, float* disps, int B, int N, int H, int W, void* stream);
 
+/* Per-pixel statistics of the head's distribution over the N planes (csrc/med_stats.hip; inference only: no gradient, not replayable --
+ * falnet_replay_op_index: -1).  p_n = softmax_n dlog0, d_n = the head's plane table, a = the FIRST index of the largest stored logit (an exact
+ * comparison), win = {n : |n - a| <= 1} within [0, N-1].  `which` selects the outputs by bit; they are written densely as out[B][K][H][W]
+ * (K = number of set bits), planar f32, in bit order:
+ *   bit 0 mean    sum p_n d_n                              (falnet_med_head_fwd's disp)
+ *   bit 1 std     sqrt(sum p_n (d_n - mean)^2), pixels     (from the centred sum)
+ *   bit 2 entropy -sum p_n ln p_n / ln N, in [0, 1]
+ *   bit 3 arg     a, an exact small integer
+ *   bit 4 conf    sum_win p_n, in (0, 1]
+ *   bit 5 peak    sum_win p_n d_n / sum_win p_n, pixels
+ * One launch for any subset; every logit is read once; no atomics, bit-identical from run to run.  Returns non-zero and writes nothing on a
+ * refused argument: which == 0 or a bit above 5, a NULL pointer, N outside [2, 128], a non-positive size (sizes: those falnet_med_head_fwd accepts). */
+#define FALNET_STAT_MEAN 1u
+#define FALNET_STAT_STD 2u
+#define FALNET_STAT_ENTROPY 4u
+#define FALNET_STAT_ARG 8u
+#define FALNET_STAT_CONF 16u
+#define FALNET_STAT_PEAK 32u
+int falnet_med_stats_fwd(const float* dlog0, const float* min_disp, const float* max_disp, unsigned which, float* out, int B, int N, int H, int W,
+                         void* stream);
+
+/* Ordered stream compaction (csrc/compact.hip; not replayable): record i of `src` (n records of rec_bytes bytes each) is kept when
+ * score[i] >= threshold -- a NaN score is dropped -- and the kept records are written to dst in index order; count_dev[0] receives their number.
+ * Per-workgroup counts, one exclusive scan, one scatter: no atomics, the result is the same bytes on every run; dst beyond the kept records is
+ * not written.  rec_bytes: 4 (a row of the planar point cloud; src and dst 4-byte aligned) or 15 (packed PLY vertex records, unaligned); anything
+ * else, n < 1 and a NULL pointer are refused with nothing written.  workspace: falnet_compact_workspace_bytes(n) bytes, 8-byte aligned as count_dev,
+ * owned by one stream at a time. */
+int64_t falnet_compact_workspace_bytes(int64_t n);
+int falnet_compact_records(const void* src, int rec_bytes, const float* score, float threshold, int64_t n, void* dst, int64_t* count_dev,
+                           void* workspace, void* stream);
+
 /* ---- losses (loss_functions.py) ; all write/accumulate a scalar in `out` (f32, device) ---- */
 /* out[0] (+)= scale * sum(mask * |a - b|) ; mask NULL or [B][1][H][W] broadcast over C (loss_functions.py:53) */
 int falnet_l1_fwd(const float* a, const float* b, const float* mask, int B, int C, int64_t HW,
