@@ -16,6 +16,7 @@ The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAM
 `--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
 `--stats KINDS` adds maps of the per-pixel disparity distribution (spread, entropy, arg-max plane, peak mass, peak disparity),
 `--pc-min-conf C` keeps only the confident vertices of the point cloud and `--disparity peak` evaluates the peak disparity, fal_net_amd/confidence.py;
+`--pseudo-lidar [--pl-beams N ...]` adds each frame's depth as a Velodyne-format scan Pseudo_lidar/<frame>.bin, fal_net_amd/pseudo_lidar.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -136,10 +137,10 @@ def _stats_kinds(v):
     return kinds
 
 
-def _min_conf(v):
+def _min_conf(v, name='--pc-min-conf'):
     c = float(v)
     if not 0.0 < c <= 1.0:
-        raise argparse.ArgumentTypeError('--pc-min-conf needs 0 < C <= 1, got {}'.format(v))
+        raise argparse.ArgumentTypeError('{} needs 0 < C <= 1, got {}'.format(name, v))
     return c
 
 
@@ -151,6 +152,83 @@ parser.add_argument('--pc-min-conf', type=_min_conf, default=None, metavar='C',
 parser.add_argument('--disparity', default='mean', choices=['mean', 'peak'],
                     help='the disparity that is evaluated and dumped: the expectation over all planes, or the expectation over the arg-max plane and its '
                          'two neighbours of the same forward (only with -mspp False -fpp False)')
+
+
+def _int_in(name, lo, hi):
+    def parse(v):
+        n = int(v)
+        if not lo <= n <= hi:
+            raise argparse.ArgumentTypeError('{} needs {} <= N <= {}, got {}'.format(name, lo, hi, v))
+        return n
+    return parse
+
+
+def _positive(name):
+    def parse(v):
+        x = float(v)
+        if not 0.0 < x < float('inf'):
+            raise argparse.ArgumentTypeError('{} needs a finite positive number, got {}'.format(name, v))
+        return x
+    return parse
+
+
+parser.add_argument('--pseudo-lidar', action='store_true',
+                    help='also write each frame\'s depth as a Velodyne-format scan Pseudo_lidar/<frame>.bin (x forward, y left, z up, intensity 1 as float32: '
+                         'what KITTI tools read), back-projected on the device (fal_net_amd/pseudo_lidar.py), and one JSON line with the point counts')
+parser.add_argument('--pl-beams', type=_int_in('--pl-beams', 0, 128), default=0, metavar='N',
+                    help='--pseudo-lidar: 0 keeps every valid pixel; N > 0 keeps the nearest point of each of N elevation x --pl-az-bins azimuth bins')
+parser.add_argument('--pl-az-bins', type=_int_in('--pl-az-bins', 1, 4096), default=1024, metavar='N', help='--pseudo-lidar with --pl-beams: azimuth bins over -45..45 degrees')
+parser.add_argument('--pl-max-depth', type=_positive('--pl-max-depth'), default=80.0, metavar='M', help='--pseudo-lidar: points beyond M metres are dropped')
+parser.add_argument('--pl-max-height', type=float, default=1.0, metavar='M', help='--pseudo-lidar: points higher than M metres above the sensor are dropped (inf: none)')
+parser.add_argument('--pl-min-conf', type=lambda v: _min_conf(v, '--pl-min-conf'), default=None, metavar='C',
+                    help='--pseudo-lidar: keep only the pixels whose probability mass around the arg-max plane (conf) is at least C (one more forward per frame)')
+parser.add_argument('--pl-calib', default=None, metavar='DIR',
+                    help='--pseudo-lidar: directory holding calib_cam_to_cam.txt and calib_velo_to_cam.txt for every frame.  Default: each frame\'s own date with '
+                         '-tn Kitti_eigen_test_original --velodyne-root, else a nominal pinhole camera at the image centre')
+LIDAR_ARGS = ('pseudo_lidar', 'pl_beams', 'pl_az_bins', 'pl_max_depth', 'pl_max_height', 'pl_min_conf', 'pl_calib')
+
+
+def check_lidar_args(a):
+    """The --pl-* switches change nothing without --pseudo-lidar: SystemExit names the one that was given."""
+    if a.pseudo_lidar:
+        if a.pl_max_height != a.pl_max_height:
+            raise SystemExit('--pl-max-height is not a number')
+        return
+    given = [n for n in LIDAR_ARGS[1:] if getattr(a, n) != parser.get_default(n)]
+    if given:
+        raise SystemExit('{} set(s) a parameter of --pseudo-lidar: add --pseudo-lidar'.format(', '.join('--' + n.replace('_', '-') for n in given)))
+
+
+def nominal_calibration(H, W):
+    """(P, fb) of a frame without calibration files: velodyne.nominal_matrix with the focal length of myUtils.width_to_focal and
+    metrics.focal_baseline('eigen', W); a width that is no KITTI width has neither, and takes the 1242-pixel camera scaled to it (dumps.camera_for_width)."""
+    from fal_net_amd import dumps, metrics, velodyne
+    from fal_net_amd.myUtils import width_to_focal
+    if W in width_to_focal:
+        focal, fb = width_to_focal[W], metrics.focal_baseline('eigen', W)
+    else:
+        focal, baseline = dumps.camera_for_width(W)
+        fb = focal * baseline
+    return velodyne.nominal_matrix(H, W, focal), fb
+
+
+def lidar_calibration(a, triples=None):
+    """Where --pseudo-lidar takes P and fb from -> (callable (frame index, H, W) -> (P, fb), a word for the output): --pl-calib DIR for every frame;
+    each frame's own date where the triples carry a calibration directory (the original split with --velodyne-root); else the nominal camera."""
+    from fal_net_amd import velodyne
+    cache = {}
+
+    def from_dir(d):
+        if d not in cache:
+            cache[d] = (velodyne.projection_matrix(d, a.velodyne_cam), velodyne.focal_baseline(d, a.velodyne_cam))
+        return cache[d]
+
+    if a.pl_calib is not None:
+        from_dir(a.pl_calib)  # a missing file stops the run here, not after the first forward
+        return (lambda i, H, W: from_dir(a.pl_calib)), 'pl-calib'
+    if triples and all(hasattr(t[2], 'calib_dir') for t in triples):
+        return (lambda i, H, W: from_dir(triples[i][2].calib_dir)), 'frame'
+    return (lambda i, H, W: nominal_calibration(H, W)), 'nominal'
 
 
 def check_confidence_args(a):
@@ -199,6 +277,7 @@ def main():
     post = 'flip' if args.f_post_process else ('ms_pp' if args.ms_post_process else 'none')
     refuse_out_of_scope(args)
     check_confidence_args(args)
+    check_lidar_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     model_dir = checkpoint_path(args)  # :119-120
     have_ckpt = os.path.isfile(model_dir)
@@ -236,7 +315,20 @@ def main():
         from fal_net_amd import confidence
         stats_writer = confidence.StatsWriter(save_path, args.stats or (), pc_min_conf=args.pc_min_conf, ply_format=args.ply_format)
 
+    lidar_writer = lidar_source = None
+
+    def make_lidar_writer(triples=None):
+        from fal_net_amd import pseudo_lidar
+        calibration, source = lidar_calibration(args, triples)
+        if source == 'nominal':
+            print('=> pseudo-LiDAR: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
+                  'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
+        return pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
+                                              max_height=args.pl_max_height, min_conf=args.pl_min_conf), source
+
     def extra_lines():
+        if lidar_writer is not None:
+            print(json.dumps({'pseudo_lidar': dict(lidar_writer.summary(), calibration=lidar_source)}))
         if sweep_writer is not None:
             print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
         if stats_writer is not None:
@@ -260,13 +352,16 @@ def main():
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
             hidden = (() if args.sweep is not None else ('sweep', 'sweep_range')) + (() if stats_writer is not None or args.disparity != 'mean' else
                                                                                   ('stats', 'pc_min_conf', 'disparity'))
+            hidden += () if args.pseudo_lidar else LIDAR_ARGS
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
+        if args.pseudo_lidar:
+            lidar_writer, lidar_source = make_lidar_writer(triples)
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
-                                 disparity=args.disparity)
+                                 disparity=args.disparity, lidar_writer=lidar_writer)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))
@@ -279,6 +374,8 @@ def main():
                           'sec_per_image': res['sec_per_image'], 'errors_txt': os.path.join(save_path, 'errors.txt')}))
         return
 
+    if args.pseudo_lidar:
+        lidar_writer, lidar_source = make_lidar_writer()
     left, _, _, _ = synthetic.synthetic_pair(1, args.height, args.width, seed=7)
     left = left.to(dev)
     max_disp = torch.tensor([args.max_disp * args.rel_baselne], device=dev).view(1, 1, 1)  # Test_KITTI.py:181-182
@@ -304,6 +401,8 @@ def main():
             inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
         if stats_writer is not None:
             inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
+        if lidar_writer is not None:
+            inference.lidar_frame(lidar_writer, 0, pan_model, left, disp, min_disp, max_disp)
     extra_lines()
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))

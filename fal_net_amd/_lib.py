@@ -197,9 +197,12 @@ SIGNATURES = {
     "falnet_epe": [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     "falnet_view_errors": [_P, _P, _F, _F, _F, _I, _I, _I, _P, _P, _P],
     "falnet_velo_project": [_P, _I, _P, _I, _I, _I, _P, _P],
+    "falnet_lidar_workspace_bytes": [_I, _I, _I, _I],
+    "falnet_velo_unproject": [_P, _D, _P, _F, _P, _F, _P, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
 }
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
-             "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64}
+             "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
+             "falnet_lidar_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

@@ -3,7 +3,8 @@ The resampling of the 1- and 3-channel maps (bilinear x2/3, nearest back) goes t
 host-side 95th percentile stays in numpy exactly as in the reference (opt-in: the exact device-side percentile of dumps.py); the two
 network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter), `evaluate(sweep_writer=...)` its views along the
 baseline (dumps.SweepWriter), `evaluate(stats_writer=...)` the statistics of its disparity distribution and its confidence-filtered point cloud
-(confidence.StatsWriter); `evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
+(confidence.StatsWriter), `evaluate(lidar_writer=...)` its disparity back-projected into a Velodyne-format scan (pseudo_lidar.PseudoLidarWriter);
+`evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
 import math
 
 import numpy as np
@@ -81,6 +82,18 @@ def stats_frame(stats_writer, i, pan_model, left, disp, min_disp, max_pix):
     stats_writer.write(i, left, disp, st, pan_model._plan(B, H, W, left.device).buf["dlog0"].shape[1])
 
 
+def lidar_frame(lidar_writer, i, pan_model, left, disp, min_disp, max_pix):
+    """Frame `i` through a pseudo_lidar.PseudoLidarWriter: `disp`, the disparity the run evaluates, back-projected with the calibration the
+    writer has for the frame.  The confidence map comes from one more disparity-only forward (confidence.from_model), only when the writer
+    filters by it."""
+    conf = None
+    if lidar_writer.min_conf is not None:
+        from . import confidence
+        conf = confidence.from_model(pan_model, left, min_disp, max_pix, ("conf",))[0]["conf"]
+    P, fb = lidar_writer.calibration(i, disp.shape[-2], disp.shape[-1])
+    lidar_writer.write(i, disp, P, fb, conf=conf)
+
+
 def peak_disparity(pan_model, left, min_disp, max_pix):
     """The forward with the peak disparity (confidence.py: the expectation over the arg-max plane and its two neighbours) in the place of
     the expectation over all planes: one disparity-only forward and one statistics launch over its logits."""
@@ -90,7 +103,7 @@ def peak_disparity(pan_model, left, min_disp, max_pix):
 
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
-             sweep_fractions=None, stats_writer=None, disparity="mean"):
+             sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -104,6 +117,7 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1).
     sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame).
     stats_writer: a confidence.StatsWriter -- every frame's distribution statistics and its confidence-filtered point cloud are written too (stats_frame).
+    lidar_writer: a pseudo_lidar.PseudoLidarWriter -- every frame's disparity is also written as a Velodyne-format scan (lidar_frame).
     disparity: "mean" (the forward's expectation) or "peak" (peak_disparity; only with post == "none": ms_pp and the flip blend two expectations)."""
     if disparity not in ("mean", "peak"):
         raise ValueError("disparity must be 'mean' or 'peak', got {!r}".format(disparity))
@@ -163,6 +177,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                     sweep_frame(sweep_writer, n, pan_model, left, mn, mx, sweep_fractions)
                 if stats_writer is not None:
                     stats_frame(stats_writer, n, pan_model, left, disp, mn, mx)
+                if lidar_writer is not None:
+                    lidar_frame(lidar_writer, n, pan_model, left, disp, mn, mx)
                 n += 1
             if log is not None and i % print_freq == 0:
                 a1 = kitti.avg[4] if table is None else table.running_mean("a1")

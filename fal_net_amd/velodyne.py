@@ -5,7 +5,7 @@ falnet_velo_project).
 
 The projection's result is defined operation by operation (include/falnet_hip.h); the host restatement it is tested against is
 tests/_velo_ref.py.  Nothing here needs a GPU to import; `project` does: like the rest of the package it has no CPU fallback and raises on a CPU
-tensor."""
+tensor.  The host side of the way back (fal_net_amd/pseudo_lidar.py: unproject) is here too: backprojection_matrix, nominal_matrix, focal_baseline."""
 import ctypes as C
 import os
 
@@ -47,6 +47,41 @@ def projection_matrix(calib_dir, cam=2):
     r_rect[:3, :3] = cam2cam["R_rect_00"].reshape(3, 3)
     p_rect = cam2cam["P_rect_0%d" % int(cam)].reshape(3, 4)
     return np.dot(np.dot(p_rect, r_rect), v2c)
+
+
+def backprojection_matrix(P):
+    """The 3 x 4 float64 Q = [M^-1 | M^-1 . P[:, 3]] of a 3 x 4 projection matrix P with M = P[:, :3]: a pixel (v, u) of depth d -- the
+    projection's third homogeneous coordinate -- is the Velodyne point X = d (Q[:, :3] . (u + 1, v + 1, 1)) - Q[:, 3] (falnet_velo_unproject)."""
+    Pm = np.asarray(P, dtype=np.float64)
+    if Pm.shape != (3, 4):
+        raise ValueError("P: expected a 3 x 4 matrix, got shape {}".format(Pm.shape))
+    m_inv = np.linalg.inv(Pm[:, :3])
+    return np.hstack((m_inv, np.dot(m_inv, Pm[:, 3:4])))
+
+
+def nominal_matrix(H, W, focal):
+    """A projection matrix for a frame without calibration: K . axes with focal length `focal`, the principal point at the image centre
+    (W / 2, H / 2), the Velodyne axes turned into the camera's (x forward -> z, y left -> -x, z up -> -y) and no translation."""
+    if not (H > 0 and W > 0 and focal > 0):
+        raise ValueError("nominal_matrix: H, W and focal must be positive, got {} {} {}".format(H, W, focal))
+    K = np.array([[float(focal), 0.0, W / 2.0], [0.0, float(focal), H / 2.0], [0.0, 0.0, 1.0]])
+    axes = np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]])
+    return np.hstack((np.dot(K, axes), np.zeros((3, 1))))
+
+
+def focal_baseline(calib_dir, cam=2):
+    """focal length times stereo baseline of the colour pair in calib_cam_to_cam.txt, f . |P_rect_02[0, 3] - P_rect_03[0, 3]| / f with f the focal
+    length of camera `cam`: depth = focal_baseline / disparity for a disparity in pixels of that camera's image."""
+    if int(cam) not in (2, 3):
+        raise ValueError("cam must be 2 or 3, got {!r}".format(cam))
+    path = os.path.join(calib_dir, "calib_cam_to_cam.txt")
+    cam2cam = read_calib_file(path)
+    for k in ("P_rect_02", "P_rect_03"):
+        if k not in cam2cam:
+            raise KeyError("{} has no numeric entry {!r}".format(path, k))
+    p2, p3 = cam2cam["P_rect_02"].reshape(3, 4), cam2cam["P_rect_03"].reshape(3, 4)
+    f = (p2 if int(cam) == 2 else p3)[0, 0]
+    return float(f * abs(p2[0, 3] - p3[0, 3]) / f)
 
 
 def load_scan(path):

@@ -695,6 +695,37 @@ int falnet_view_errors(const float* out, const float* label, float mean_r, float
  * no point lands and where the minimum is negative.  n_points = 0 gives an all-zero map.  H W < 2^31; every entry of P finite.  Not replayable. */
 int falnet_velo_project(const float* points, int n_points, const double* P, int H, int W, int vel_depth, float* depth_out, void* stream);
 
+/* ---- Pseudo-LiDAR (csrc/lidar.hip; fal_net_amd/pseudo_lidar.py) --------------------------------------------------------------------------------
+ * The inverse of falnet_velo_project: an (H, W) f32 depth or disparity map on the device back-projected into Velodyne-format records, x forward,
+ * y left, z up, intensity as four f32 -- the 16-byte point of a KITTI .bin file.  Q: 12 doubles on the HOST, the row-major 3 x 4 back-projection
+ * matrix [M^-1 | M^-1 P[:,3]] of a velodyne-to-image matrix P with M = P[:, :3], passed on to the kernels by value.  Per pixel (v, u), all arithmetic
+ * f64 in the stated order with no fused multiply-add unless marked f32:
+ *   1. fb > 0: the map is a disparity, valid only if disp > 0, d = (float)(fb / (double)disp); fb == 0: the map is the depth d (the projection's
+ *      third homogeneous coordinate, what falnet_velo_project writes);
+ *   2. keep when d > min_depth && d <= max_depth (f32 compares: NaN and infinity fail);
+ *   3. score (H x W f32, may be NULL): keep when score >= threshold (a NaN score is dropped);
+ *   4. r_i = (Q[i][0] (u + 1) + Q[i][1] (v + 1)) + Q[i][2], X_i = d r_i - Q[i][3], (x, y, z) = (float)X_i; keep when x > 0 && z <= max_height
+ *      (max_height may be +infinity);
+ *   5. the record is x, y, z, intensity: intensity_map's value at the pixel (H x W f32), or the constant `intensity` when the map is NULL.
+ * beams == 0 (dense): the kept records in row-major pixel order.  1 <= beams <= 128, 1 <= az_bins <= 4096 (beam mode): elev_edges_dev / az_edges_dev
+ * are non-decreasing f64 tables ON THE DEVICE of beams + 1 tangents of the elevation edges and az_bins + 1 tangents of the azimuth edges; from the
+ * f32 record widened back to f64, rho = sqrt(x x + y y), e = z / rho, a = y / x, beam = #{k : e >= te[k]} - 1, col = #{j : a >= ta[j]} - 1
+ * (searchsorted(side='right') - 1; a NaN counts nothing); a point whose beam or col is outside its range is dropped.  Each bin keeps the point of the
+ * smallest 64-bit key (bits(d) << 32) | (v W + u) -- nearest depth first, then the lowest pixel index -- through an integer atomicMin on a u64: no
+ * floating-point atomics.  The winners are written in bin order, beam major.  Either mode is bit-identical from run to run and to the host
+ * restatement (tests/_lidar_ref.py): both sides do only correctly rounded + - * / sqrt and comparisons against the same table values.
+ * out_points: up to `capacity` records, 16-byte aligned (one record is one 16-byte store); count_dev: one int64 on the device, the TRUE number of kept
+ * records -- where it exceeds capacity only the first `capacity` records are written and the call still returns 0; bytes beyond the written records
+ * are not touched.  workspace: falnet_lidar_workspace_bytes(H, W, beams, az_bins) bytes, 8-byte aligned as count_dev and the tables (beam mode fills
+ * its key table itself).  Refused with nothing written: a NULL map, Q, count_dev or workspace, NULL tables in beam mode, a NULL output with
+ * capacity > 0, H W < 1 or >= 2^31, beams or az_bins out of range (az_bins is checked in dense mode too), a max_depth that is not finite, a negative
+ * or non-finite fb, a NaN min_depth / max_height / threshold, a non-finite entry of Q, capacity < 0, a misaligned pointer.
+ * falnet_lidar_workspace_bytes is 0 for a refused shape.  Not replayable. */
+int64_t falnet_lidar_workspace_bytes(int H, int W, int beams, int az_bins);
+int falnet_velo_unproject(const float* map, double fb, const float* score, float threshold, const float* intensity_map, float intensity, const double* Q,
+                          float min_depth, float max_depth, float max_height, int H, int W, int beams, int az_bins, const double* elev_edges_dev,
+                          const double* az_edges_dev, float* out_points, int64_t capacity, int64_t* count_dev, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
