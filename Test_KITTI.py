@@ -16,6 +16,8 @@ The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAM
 `--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
 `--stats KINDS` adds maps of the per-pixel disparity distribution (spread, entropy, arg-max plane, peak mass, peak disparity),
 `--pc-min-conf C` keeps only the confident vertices of the point cloud and `--disparity peak` evaluates the peak disparity, fal_net_amd/confidence.py;
+`--sparsification SCORES [--sparsification-steps S]` writes sparsification.txt: AUSE / AURG of the named confidence scores against the depth errors,
+fal_net_amd/sparsification.py;
 `--pseudo-lidar [--pl-beams N ...]` adds each frame's depth as a Velodyne-format scan Pseudo_lidar/<frame>.bin, fal_net_amd/pseudo_lidar.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
@@ -199,6 +201,53 @@ def check_lidar_args(a):
         raise SystemExit('{} set(s) a parameter of --pseudo-lidar: add --pseudo-lidar'.format(', '.join('--' + n.replace('_', '-') for n in given)))
 
 
+SPARSIFICATION_SCORES = ('std', 'entropy', 'conf', 'relstd')  # fal_net_amd/sparsification.py: SCORES
+
+
+def _sparsification_scores(v):
+    names = [k for k in v.split(',') if k]
+    bad = [k for k in names if k not in SPARSIFICATION_SCORES]
+    if bad or not names or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError('--sparsification takes a comma-separated subset of {} (each once), got {!r}'.format(','.join(SPARSIFICATION_SCORES), v))
+    return names
+
+
+parser.add_argument('--sparsification', type=_sparsification_scores, default=None, metavar='SCORES',
+                    help='comma-separated subset of std,entropy,conf,relstd: per frame with ground truth, remove the pixels in order of each score and of the true '
+                         'error and recompute abs_rel, rms and d1 = 1 - a1 on the rest (fal_net_amd/sparsification.py: sorted and summed on the device); writes '
+                         'sparsification.txt with AUSE and AURG per score and the mean curves, and one JSON line.  Dataset mode with -eval True only')
+parser.add_argument('--sparsification-steps', type=_int_in('--sparsification-steps', 2, 100), default=None, metavar='S',
+                    help='--sparsification: the number of cuts of every curve; cut j removes the j / S most uncertain pixels (default 50)')
+SPARSIFICATION_ARGS = ('sparsification', 'sparsification_steps')
+
+
+def check_sparsification_args(a, dataset_mode):
+    """--sparsification needs ground truth; --sparsification-steps changes nothing without it.  SystemExit says which."""
+    if a.sparsification is None:
+        if a.sparsification_steps is not None:
+            raise SystemExit('--sparsification-steps sets a parameter of --sparsification: add --sparsification')
+        return
+    if not dataset_mode:
+        raise SystemExit('--sparsification compares the scores with the depth errors, and synthetic mode has no ground truth: give a dataset (-d <root>)')
+    if not a.evaluate:
+        raise SystemExit('--sparsification needs the depth errors: run with -eval True')
+
+
+def write_sparsification(path, res):
+    """sparsification.txt: one line per score with AUSE and AURG of the three metrics (means over the frames with ground truth), then the mean curves."""
+    with open(path, 'w') as f:
+        f.write('Sparsification over {} frames, {} cuts (AUSE: area between score and oracle, lower is better; AURG: area between random and score, '
+                'higher is better)\n'.format(res['frames'], res['steps']))
+        for k in res['names']:
+            f.write('{:>8s}: '.format(k) + '  '.join('ause_{0} {1:.6f} aurg_{0} {2:.6f}'.format(m, res['ause_mean'][k][m], res['aurg_mean'][k][m])
+                                                    for m in res['metrics']) + '\n')
+        f.write('\nMean curves (fraction removed: 0, 1/S, ..., (S-1)/S)\n')
+        for m in res['metrics']:
+            f.write('{:>8s} {:>8s}: '.format('oracle', m) + ' '.join('{:.6f}'.format(v) for v in res['oracle_mean'][m]) + '\n')
+            for k in res['names']:
+                f.write('{:>8s} {:>8s}: '.format(k, m) + ' '.join('{:.6f}'.format(v) for v in res['curves_mean'][k][m]) + '\n')
+
+
 def nominal_calibration(H, W):
     """(P, fb) of a frame without calibration files: velodyne.nominal_matrix with the focal length of myUtils.width_to_focal and
     metrics.focal_baseline('eigen', W); a width that is no KITTI width has neither, and takes the 1242-pixel camera scaled to it (dumps.camera_for_width)."""
@@ -279,6 +328,7 @@ def main():
     check_confidence_args(args)
     check_lidar_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
+    check_sparsification_args(args, dataset_mode)
     model_dir = checkpoint_path(args)  # :119-120
     have_ckpt = os.path.isfile(model_dir)
     if args.checkpoint and not have_ckpt:
@@ -326,7 +376,13 @@ def main():
         return pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
                                               max_height=args.pl_max_height, min_conf=args.pl_min_conf), source
 
+    sparsification = None
+
     def extra_lines():
+        if sparsification is not None:
+            print(json.dumps({'sparsification': {'scores': res['sparsification']['names'], 'steps': res['sparsification']['steps'],
+                                                 'frames': res['sparsification']['frames'], 'ause': res['sparsification']['ause_mean'],
+                                                 'aurg': res['sparsification']['aurg_mean'], 'file': os.path.join(save_path, 'sparsification.txt')}}))
         if lidar_writer is not None:
             print(json.dumps({'pseudo_lidar': dict(lidar_writer.summary(), calibration=lidar_source)}))
         if sweep_writer is not None:
@@ -353,15 +409,21 @@ def main():
             hidden = (() if args.sweep is not None else ('sweep', 'sweep_range')) + (() if stats_writer is not None or args.disparity != 'mean' else
                                                                                   ('stats', 'pc_min_conf', 'disparity'))
             hidden += () if args.pseudo_lidar else LIDAR_ARGS
+            hidden += () if args.sparsification is not None else SPARSIFICATION_ARGS
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         if args.pseudo_lidar:
             lidar_writer, lidar_source = make_lidar_writer(triples)
+        if args.sparsification is not None:
+            from fal_net_amd import sparsification as SP
+            sparsification = SP.SparsificationTable(len(triples), args.sparsification, args.sparsification_steps or SP.DEFAULT_STEPS, dev)
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
-                                 disparity=args.disparity, lidar_writer=lidar_writer)
+                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification)
+        if sparsification is not None:
+            write_sparsification(os.path.join(save_path, 'sparsification.txt'), res['sparsification'])
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))

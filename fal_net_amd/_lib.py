@@ -99,6 +99,10 @@ class Aug(C.Structure):  # falnet_aug_t: one sample of falnet_augment_batch
                 ("cb", (C.c_double * 3) * 2)]
 
 
+class Scores(C.Structure):  # falnet_scores_t: the score maps of falnet_sparsify, passed by value
+    _fields_ = [("map", C.c_void_p * 4), ("sign", C.c_int32 * 4), ("n", C.c_int32)]
+
+
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 # name -> argtypes (restype int unless listed in _RESTYPES); mirrors include/falnet_hip.h one to one
 SIGNATURES = {
@@ -199,10 +203,15 @@ SIGNATURES = {
     "falnet_velo_project": [_P, _I, _P, _I, _I, _I, _P, _P],
     "falnet_lidar_workspace_bytes": [_I, _I, _I, _I],
     "falnet_velo_unproject": [_P, _D, _P, _F, _P, _F, _P, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
+    "falnet_sort_u32_workspace_bytes": [_L, _I],
+    "falnet_sort_u32": [_P, _L, _I, _P, _P, _P],
+    "falnet_sparsify_workspace_bytes": [_I, _I, _I],
+    "falnet_sparsify": [_P, _P, _I, _I, _I, _D, _P, _D, _D, Scores, _I, _P, _P, _P],
 }
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
-             "falnet_lidar_workspace_bytes": C.c_int64}
+             "falnet_lidar_workspace_bytes": C.c_int64, "falnet_sort_u32_workspace_bytes": C.c_int64,
+             "falnet_sparsify_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

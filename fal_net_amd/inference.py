@@ -4,6 +4,7 @@ host-side 95th percentile stays in numpy exactly as in the reference (opt-in: th
 network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter), `evaluate(sweep_writer=...)` its views along the
 baseline (dumps.SweepWriter), `evaluate(stats_writer=...)` the statistics of its disparity distribution and its confidence-filtered point cloud
 (confidence.StatsWriter), `evaluate(lidar_writer=...)` its disparity back-projected into a Velodyne-format scan (pseudo_lidar.PseudoLidarWriter);
+`evaluate(sparsification=...)` the sparsification curves of its confidence scores against its depth errors (sparsification.SparsificationTable);
 `evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
 import math
 
@@ -94,6 +95,17 @@ def lidar_frame(lidar_writer, i, pan_model, left, disp, min_disp, max_pix):
     lidar_writer.write(i, disp, P, fb, conf=conf)
 
 
+def sparsify_frame(table, pan_model, left, disp, target, mode, use_median, min_disp, max_pix):
+    """One frame with ground truth into the next row of a sparsification.SparsificationTable.  The errors are those of `disp`, the disparity the
+    run evaluates AFTER post-processing; the scores (table.names, from sparsification.SCORES) are statistics of the logits of one more
+    disparity-only forward of the plain view (confidence.from_model), as in stats_frame: with ms_pp or the flip post-processing the scores
+    describe the first of the two blended forwards."""
+    from . import confidence
+    from . import sparsification as S
+    st, _ = confidence.from_model(pan_model, left, min_disp, max_pix, S.stats_needed(table.names))
+    S.curves(disp, target, mode, S.score_maps(st, table.names), use_median=use_median, steps=table.steps, out=table.row(table.n))
+
+
 def peak_disparity(pan_model, left, min_disp, max_pix):
     """The forward with the peak disparity (confidence.py: the expectation over the arg-max plane and its two neighbours) in the place of
     the expectation over all planes: one disparity-only forward and one statistics launch over its logits."""
@@ -103,14 +115,14 @@ def peak_disparity(pan_model, left, min_disp, max_pix):
 
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
-             sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None):
+             sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None, sparsification=None):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
     datasets.StereoValDataset; gt is a disparity map (Kitti2015) or a depth map (Eigen split, listdataset_test.py:43-46 reads both
     as uint16 / 256); with datasets.StereoEvalDataset it may also be the depth map of a '.npy' file or a datasets.VeloScan (a raw Velodyne
     scan and its projection matrix: the depth map is then velodyne.project of it on the device) -- the original Eigen split.
-    Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'}.
+    Returns {'epe', 'kitti': {name: value}, 'n', 'sec_per_image'} (and 'sparsification' with `sparsification`).
     writer: a dumps.FrameWriter -- every frame's outputs are also written to disk (:211-253), after the timed region and after the metrics;
     where it wants the synthesised view or the occlusion masks the model runs once more with ret_pan / ret_subocc.  device_percentile: ms_pp.
     device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
@@ -118,6 +130,9 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame).
     stats_writer: a confidence.StatsWriter -- every frame's distribution statistics and its confidence-filtered point cloud are written too (stats_frame).
     lidar_writer: a pseudo_lidar.PseudoLidarWriter -- every frame's disparity is also written as a Velodyne-format scan (lidar_frame).
+    sparsification: a sparsification.SparsificationTable built with the score names -- every frame with ground truth also leaves its sparsification
+    curves in the table's next row (sparsify_frame: the errors of `disp` after post-processing, the scores from one more disparity-only forward), with
+    and without device_metrics; the table is read once after the last frame and its result() is returned under 'sparsification'.
     disparity: "mean" (the forward's expectation) or "peak" (peak_disparity; only with post == "none": ms_pp and the flip blend two expectations)."""
     if disparity not in ("mean", "peak"):
         raise ValueError("disparity must be 'mean' or 'peak', got {!r}".format(disparity))
@@ -171,6 +186,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                         else:  # Eigen split: :258-263
                             gt_depth, pred_depth = utils.disps_to_depths_kitti(t_np, p_np)
                         kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
+                    if sparsification is not None:
+                        sparsify_frame(sparsification, pan_model, left, disp, target, "kitti2015" if data_name == "Kitti2015" else "eigen", use_median, mn, mx)
                 if writer is not None:
                     dump_frame(writer, n, pan_model, left, disp, mn, mx)
                 if sweep_writer is not None:
@@ -189,5 +206,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
             epes.update(float(e), 1)
         for errs in res["depth"]:
             kitti.update(errs, 1)
-    return {"epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg])), "kitti_table": repr(kitti), "n": n,
-            "sec_per_image": batch_time.avg}
+    out = {"epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg])), "kitti_table": repr(kitti), "n": n,
+           "sec_per_image": batch_time.avg}
+    if sparsification is not None:
+        out["sparsification"] = sparsification.result()
+    return out

@@ -726,6 +726,38 @@ int falnet_velo_unproject(const float* map, double fb, const float* score, float
                           float min_depth, float max_depth, float max_height, int H, int W, int beams, int az_bins, const double* elev_edges_dev,
                           const double* az_edges_dev, float* out_points, int64_t capacity, int64_t* count_dev, void* workspace, void* stream);
 
+/* ---- stable segmented argsort (csrc/sort.hip; fal_net_amd/sparsification.py: argsort_u32) ---------------------------------------------------
+ * keys: `segments` independent arrays of n u32 keys each, keys[s * n + i], 1 <= segments <= 8, n <= 2^24, on the device, never written.
+ * perm[s * n + r] = the index i of the element of segment s that has rank r in ascending key order; equal keys stay in ascending index order
+ * (np.argsort(kind="stable")).  Four least-significant-digit passes of 8 bits, three launches each, every segment in the same launches; no output
+ * position depends on an atomic: two calls write the same bytes.  workspace: falnet_sort_u32_workspace_bytes(n, segments) bytes (0 for a refused
+ * shape and for n = 0), 8-byte aligned as perm.  n = 0 returns 0 and writes nothing.  Refused before any launch: n < 0 or n > 2^24, segments
+ * outside 1 .. 8, a NULL pointer, a perm or workspace that is not 8-byte aligned.  Not replayable. */
+int64_t falnet_sort_u32_workspace_bytes(int64_t n, int segments);
+int falnet_sort_u32(const uint32_t* keys, int64_t n, int segments, uint32_t* perm, void* workspace, void* stream);
+
+/* ---- sparsification curves (csrc/sparsify.hip; fal_net_amd/sparsification.py) -----------------------------------------------------------------
+ * pred_disp, gt, H, W, mode, fb, scale (may be NULL), min_d, max_d: exactly the arguments of falnet_depth_errors; the pixels that count, their
+ * number n and their depths g, p (scaled, then clamped) are that function's.  The counted pixels are numbered 0 .. n - 1 in row-major order of the
+ * region.  Per pixel in f64: e_abs = |g - p| / g, e_sq = (g - p)^2, t = max(g / p, p / g).  An f32 x has the key k(x) = 0xFFFFFFFF for a NaN,
+ * bits ^ 0xFFFFFFFF with the sign bit set, bits | 0x80000000 otherwise; an ordering is the stable ascending sort of ~k(x): the largest x first,
+ * NaN before everything, ties in pixel-number order.  There are scores.n + 3 orderings: x = map[s] (sign +1: larger is more uncertain) or -map[s]
+ * (sign -1: larger is more confident) at the pixel's place in the H x W map, then the oracles x = (float)e_abs, (float)e_sq, (float)t.
+ * Cut j of `steps` = S (2 .. 100) removes the first r_j = (j n) / S pixels of an ordering and keeps n_j = n - r_j; of the kept pixels
+ * abs_rel_j = sum e_abs / n_j, rms_j = sqrt(sum e_sq / n_j), d1_j = (n_j - #{t < 1.25}) / n_j.
+ * row: 1 + (3 scores.n + 3) S doubles -- n; per score its abs_rel, rms and d1 curves; the oracle abs_rel, rms and d1 curves (each from the
+ * ordering of its own metric); n = 0 gives NaN curves.  Sums have a fixed partition and order: two calls give the same bits.
+ * workspace: falnet_sparsify_workspace_bytes(H, W, scores.n) bytes (0 for a refused shape), 8-byte aligned as row and scale.  Refused with nothing
+ * written: what falnet_depth_errors refuses, H W > 2^24, steps or scores.n out of range, a sign that is not +1 or -1, a NULL map.  Not replayable. */
+typedef struct {
+    const float* map[4]; /* H x W f32 on the device */
+    int sign[4];         /* +1 or -1 */
+    int n;               /* 0 .. 4 */
+} falnet_scores_t;
+int64_t falnet_sparsify_workspace_bytes(int H, int W, int n_scores);
+int falnet_sparsify(const float* pred_disp, const float* gt, int H, int W, int mode, double fb, const double* scale, double min_d, double max_d,
+                    falnet_scores_t scores, int steps, double* row, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
