@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libfalnet_hip.so")
-SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_stats.hip", "compact.hip", "losses.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "velo.hip", "lidar.hip", "sort.hip", "sparsify.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
+SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_stats.hip", "compact.hip", "losses.hip", "adam.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "velo.hip", "lidar.hip", "sort.hip", "sparsify.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  The MED head kernels are f32 VALU work per pixel and plane: the SLP vectoriser pairs independent scalar
@@ -60,7 +60,7 @@ def build_ab(tag="ab", defines=(), verbose=True, raw=()):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
     jobs = []
     for src in SOURCES:
         path = os.path.join(CSRC, src)

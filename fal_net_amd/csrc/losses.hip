@@ -1,5 +1,5 @@
-// HBM-bound loss / optimiser kernels for gfx950 (reference: loss_functions.py:52-101,
-// Train_Stage1_K.py:180,248-262, Train_Stage2_K.py:248-253,319-324).  All f32 arithmetic.
+// HBM-bound loss and loss-scale kernels for gfx950 (reference: loss_functions.py:52-101,
+// Train_Stage1_K.py:248-262, Train_Stage2_K.py:248-253,319-324).  All f32 arithmetic.
 // Reductions: grid-stride partial sums in registers -> wave shuffle -> one LDS hop -> ONE float
 // atomic per workgroup on the scalar (grids capped at RED_BLOCKS so the single-address atomic
 // chain stays in the microsecond range; cdna guide G12).
@@ -453,191 +453,6 @@ __global__ __launch_bounds__(RED_THREADS) void mirror_weight_kernel(const float*
     }
 }
 
-// ------------------------------------------------------------------ fused flat Adam (torch.optim.Adam, Train_Stage1_K.py:180)
-// 7 f32 streams per element (read p,g,m,v; write p,m,v): 28 B/param, pure HBM streaming, float4 lanes.
-__global__ __launch_bounds__(RED_THREADS) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                           float step_size, float b1, float b2, float eps,
-                                                           float rsqrt_bc2, float grad_scale) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-        float* P = &pp.x;
-        float* G = &gg.x;
-        float* M = &mm.x;
-        float* V = &vv.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gr = G[j] * grad_scale;
-            M[j] = b1 * M[j] + (1.f - b1) * gr;
-            V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
-            P[j] -= step_size * M[j] / (sqrtf(V[j]) * rsqrt_bc2 + eps);
-        }
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        const float gr = g[i] * grad_scale;
-        const float mi = b1 * m[i] + (1.f - b1) * gr, vi = b2 * v[i] + (1.f - b2) * gr * gr;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step_size * mi / (sqrtf(vi) * rsqrt_bc2 + eps);
-    }
-}
-
-// Adam with its hyper-state on the device: state = {lr, t}.  A captured hipGraph replays the same launch
-// arguments, so the step count (bias corrections) must advance in device memory, not in a kernel argument.
-__global__ __launch_bounds__(RED_THREADS) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                               const float* __restrict__ state, float b1, float b2, float eps,
-                                                               float grad_scale, const float* __restrict__ scaler) {
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;  // non-finite gradient somewhere: skip the whole update (uniform over the grid)
-        grad_scale /= scaler[0];
-    }
-    const float lr = state[0];
-    const float t = state[1] + 1.0f;
-    const float step_size = lr / (1.0f - powf(b1, t));
-    const float rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-        float* P = &pp.x;
-        float* G = &gg.x;
-        float* M = &mm.x;
-        float* V = &vv.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gr = G[j] * grad_scale;
-            M[j] = b1 * M[j] + (1.f - b1) * gr;
-            V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
-            P[j] -= step_size * M[j] / (sqrtf(V[j]) * rsqrt_bc2 + eps);
-        }
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-}
-// The same update over a list of element ranges of the flat buffer (the parameters falnet_adam_pack_batched does not own: biases, the two
-// factors of the composed logits weights): ranges[2 r] = first element, ranges[2 r + 1] = count; blockIdx.y = range.
-__global__ __launch_bounds__(RED_THREADS) void adam_ranges_kernel(float* __restrict__ p, int64_t g_off, int64_t m_off, int64_t v_off,
-                                                                  const int64_t* __restrict__ ranges, const float* __restrict__ state, float b1, float b2,
-                                                                  float eps, float grad_scale, const float* __restrict__ scaler) {
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;
-        grad_scale /= scaler[0];
-    }
-    const float t = state[1] + 1.0f;
-    const float step_size = state[0] / (1.0f - powf(b1, t));
-    const float rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
-    const int64_t beg = ranges[2 * blockIdx.y], cnt = ranges[2 * blockIdx.y + 1];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        float* wp = p + beg + i;
-        const float gr = wp[g_off] * grad_scale;
-        const float m = b1 * wp[m_off] + (1.f - b1) * gr;
-        const float v = b2 * wp[v_off] + (1.f - b2) * gr * gr;
-        *wp -= step_size * m / (sqrtf(v) * rsqrt_bc2 + eps);
-        wp[m_off] = m;
-        wp[v_off] = v;
-    }
-}
-__global__ void adam_tick_kernel(float* state, const float* __restrict__ scaler) {
-    if (scaler == nullptr || scaler[2] == 0.f) state[1] += 1.0f;  // a skipped (overflowed) step does not count
-}
-
-// ---- weight decay / bias decay (torch.optim.Adam's L2 form, NOT AdamW; the two param groups of Train_Stage1_K.py:177-180) ----
-// gr = g * grad_scale + decay * p, then the moments and the step exactly as above.  The decay differs per PARAMETER (bias_decay for the
-// biases, weight_decay for the weights) and the flat buffer does not know which element is which, so both kernels read it from a small
-// device table.  No extra memory stream: p is loaded anyway.  The 16-B padding elements between slices hold p = g = 0: gr = 0, m = v = 0
-// and the step is 0 / (0 + eps) = 0, so they stay exactly 0 whatever decay their segment carries.
-// gr is formed in DOUBLE from a double decay and rounded to f32 once.  Where g and decay * p cancel (|gr| << |g|; with real gradients a few
-// elements per million), an f32 sum -- or a decay rounded to f32 -- leaves gr with an absolute error of 2^-24 |g|, and while the second
-// moment is still young the step lr * m / (sqrt(v) + eps) ~ lr * gr / |gr| amplifies it: torch's own f32 Adam lands an order of magnitude outside the
-// tests' float64 bound there, this form stays inside it.  Three conversions and one f64 FMA per element beside 28 B of HBM traffic.
-__device__ __forceinline__ float decayed_grad(float g, float grad_scale, double decay, float w) {
-    return (float)fma(decay, (double)w, (double)g * (double)grad_scale);  // (the product of two floats is exact in double)
-}
-// Range form: decays[r] belongs to ranges[2 r], ranges[2 r + 1] (a range never spans two parameters: plan.py cuts them at the boundaries).
-__global__ __launch_bounds__(RED_THREADS) void adam_ranges_wd_kernel(float* __restrict__ p, int64_t g_off, int64_t m_off, int64_t v_off,
-                                                                     const int64_t* __restrict__ ranges, const double* __restrict__ decays,
-                                                                     const float* __restrict__ state, float b1, float b2, float eps, float grad_scale,
-                                                                     const float* __restrict__ scaler) {
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;  // skipped as a whole, decay included
-        grad_scale /= scaler[0];
-    }
-    const float t = state[1] + 1.0f;
-    const float step_size = state[0] / (1.0f - powf(b1, t));
-    const float rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
-    const int64_t beg = ranges[2 * blockIdx.y], cnt = ranges[2 * blockIdx.y + 1];
-    const double decay = decays[blockIdx.y];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        float* wp = p + beg + i;
-        const float w = *wp;
-        const float gr = decayed_grad(wp[g_off], grad_scale, decay, w);
-        const float m = b1 * wp[m_off] + (1.f - b1) * gr;
-        const float v = b2 * wp[v_off] + (1.f - b2) * gr * gr;
-        *wp = w - step_size * m / (sqrtf(v) * rsqrt_bc2 + eps);
-        wp[m_off] = m;
-        wp[v_off] = v;
-    }
-}
-// Flat form (the stand-alone update: no plan yet, pack fusion off, stream capture): the float4 streaming loop of adam_dev_kernel; the
-// decay of a float4 comes from a segment table -- seg_end[s] = exclusive end ELEMENT of segment s (ascending, multiples of 4 because the
-// slices are 16-B aligned, seg_end[n_seg - 1] >= n), seg_decay[s] its decay -- staged in LDS once per block and searched per float4
-// (<= 10 LDS reads beside 7 x 16 B of HBM traffic).  An index past the last end falls into the last segment: the lookup cannot leave the table.
-#define ADAM_WD_MAX_SEG 1024
-__global__ __launch_bounds__(RED_THREADS) void adam_dev_wd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                  float* __restrict__ v, int64_t n, const int64_t* __restrict__ seg_end,
-                                                                  const double* __restrict__ seg_decay, int n_seg, const float* __restrict__ state,
-                                                                  float b1, float b2, float eps, float grad_scale, const float* __restrict__ scaler) {
-    __shared__ int64_t s_end4[ADAM_WD_MAX_SEG];  // in float4 units
-    __shared__ double s_decay[ADAM_WD_MAX_SEG];
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;  // grid-uniform, before the barrier
-        grad_scale /= scaler[0];
-    }
-    for (int s = threadIdx.x; s < n_seg; s += blockDim.x) {
-        s_end4[s] = seg_end[s] >> 2;
-        s_decay[s] = seg_decay[s];
-    }
-    __syncthreads();
-    const float lr = state[0];
-    const float t = state[1] + 1.0f;
-    const float step_size = lr / (1.0f - powf(b1, t));
-    const float rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = n_seg - 1;  // first segment whose end lies beyond float4 i
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (i < s_end4[mid]) hi = mid;
-            else lo = mid + 1;
-        }
-        const double decay = s_decay[lo];
-        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-        float* P = &pp.x;
-        float* G = &gg.x;
-        float* M = &mm.x;
-        float* V = &vv.x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float gr = decayed_grad(G[j], grad_scale, decay, P[j]);
-            M[j] = b1 * M[j] + (1.f - b1) * gr;
-            V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
-            P[j] -= step_size * M[j] / (sqrtf(V[j]) * rsqrt_bc2 + eps);
-        }
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-}
-
 // ------------------------------------------------------------------ dynamic loss scale of the f16 path (GradScaler semantics, device-resident)
 // scaler = {scale, good_steps, overflow_flag, skipped_steps}.  The guard raises the flag when any element of the (all-reduced)
 // flat gradient is inf / NaN; the guarded Adam then leaves p, m, v and the step count untouched; the update kernel halves the scale
@@ -820,71 +635,6 @@ extern "C" int falnet_mirror_weight(const float* occ, const float* rowmax, float
     FALNET_RETURN_LAUNCH();
 }
 
-extern "C" int falnet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
-                                float eps, int step, float grad_scale, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "adam_step: bad argument");
-    FALNET_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: buffers must be 16-B aligned");
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    const float step_size = (float)(lr / bc1), rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    hipLaunchKernelGGL(adam_kernel, dim3(2048), dim3(RED_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, step_size, b1,
-                       b2, eps, rsqrt_bc2, grad_scale);
-    FALNET_RETURN_LAUNCH();
-}
-
-static int adam_dev_launch(float* p, const float* g, float* m, float* v, int64_t n, float* state, float b1, float b2, float eps, float grad_scale,
-                           const float* scaler, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(p && g && m && v && state && n > 0 && (n & 3) == 0, "adam_step_dev: bad argument (n must be a multiple of 4)");
-    FALNET_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_dev: buffers must be 16-B aligned");
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(2048), dim3(RED_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, state, b1, b2, eps, grad_scale, scaler);
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, scaler);
-    FALNET_RETURN_LAUNCH();
-}
-extern "C" int falnet_adam_ranges(float* p, int64_t g_off, int64_t m_off, int64_t v_off, const int64_t* ranges_dev, int n_ranges, const float* state,
-                                  float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(p && ranges_dev && n_ranges > 0 && state && g_off != 0 && m_off != 0 && v_off != 0, "adam_ranges: bad argument");
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3(48, n_ranges), dim3(RED_THREADS), 0, (hipStream_t)stream, p, g_off, m_off, v_off, ranges_dev, state, b1, b2, eps,
-                       grad_scale, scaler);
-    FALNET_RETURN_LAUNCH();
-}
-extern "C" int falnet_adam_tick(float* state, const float* scaler, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(state, "adam_tick: bad argument");
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, scaler);
-    FALNET_RETURN_LAUNCH();
-}
-extern "C" int falnet_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, float b1, float b2,
-                                    float eps, float grad_scale, void* stream) {
-    return adam_dev_launch(p, g, m, v, n, state, b1, b2, eps, grad_scale, nullptr, stream);
-}
-extern "C" int falnet_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float* state, float b1, float b2,
-                                        float eps, float grad_scale, const float* scaler, void* stream) {
-    FALNET_CHECK_ARG(scaler, "adam_step_guarded: scaler is NULL");
-    return adam_dev_launch(p, g, m, v, n, state, b1, b2, eps, grad_scale, scaler, stream);
-}
-extern "C" int falnet_adam_ranges_wd(float* p, int64_t g_off, int64_t m_off, int64_t v_off, const int64_t* ranges_dev, const double* decays_dev,
-                                     int n_ranges, const float* state, float b1, float b2, float eps, float grad_scale, const float* scaler,
-                                     void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(p && ranges_dev && decays_dev && n_ranges > 0 && n_ranges <= 65535 && state && g_off != 0 && m_off != 0 && v_off != 0,
-                     "adam_ranges_wd: bad argument");
-    hipLaunchKernelGGL(adam_ranges_wd_kernel, dim3(48, n_ranges), dim3(RED_THREADS), 0, (hipStream_t)stream, p, g_off, m_off, v_off, ranges_dev, decays_dev,
-                       state, b1, b2, eps, grad_scale, scaler);
-    FALNET_RETURN_LAUNCH();
-}
-extern "C" int falnet_adam_step_wd(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end_dev, const double* seg_decay_dev,
-                                   int n_seg, float* state, float b1, float b2, float eps, float grad_scale, const float* scaler, void* stream) {
-    FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(p && g && m && v && state && n > 0 && (n & 3) == 0, "adam_step_wd: bad argument (n must be a multiple of 4)");
-    FALNET_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_wd: buffers must be 16-B aligned");
-    FALNET_CHECK_ARG(seg_end_dev && seg_decay_dev && n_seg > 0 && n_seg <= ADAM_WD_MAX_SEG, "adam_step_wd: 1 .. %d segments", ADAM_WD_MAX_SEG);
-    hipLaunchKernelGGL(adam_dev_wd_kernel, dim3(2048), dim3(RED_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, seg_end_dev, seg_decay_dev, n_seg, state,
-                       b1, b2, eps, grad_scale, scaler);
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, scaler);
-    FALNET_RETURN_LAUNCH();
-}
 // Tail of a fused training step: out = {S0 + a * S1, S0, S1}, then S0 = S1 = 0 for the next step (one launch instead of a clone, an
 // axpy and a fill).
 __global__ void step_scalars_kernel(float* S, float a, float* out) {

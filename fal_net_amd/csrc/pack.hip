@@ -2,27 +2,25 @@
 // weights of the deconv layers), and the optimiser step fused with the re-pack (torch.optim.Adam with or without weight decay).
 // Not one of the autotuned sources (ops.py: _TUNE_SOURCES): a change here leaves every cached convolution choice valid.
 #include <type_traits>
+#include "adam.h"
 #include "common.h"
 
 // One block = one 32(cout) x 32(packed cin) tile of one layer, all taps, staged through LDS: the OIHW reads are
 // runs of taps*32 contiguous floats, the wf rows ([co][tap][32 cin]) and wd rows ([cin][tap][32 cout]) are written as
 // 32 contiguous elements.  (The element-per-thread version gathered with stride `taps` and scattered 2-byte writes.)
-// ADAM: the tile's master weights are UPDATED while they are loaded (torch.optim.Adam, Train_Stage1_K.py:177-180: the same arithmetic as
-// losses.hip: adam_dev_kernel) -- every real (co, ci, tap) element of a layer belongs to exactly one tile, so the optimiser step of all
+// ADAM: the tile's master weights are UPDATED while they are loaded (torch.optim.Adam, Train_Stage1_K.py:177-180: adam.h, the update the
+// kernels of adam.hip apply) -- every real (co, ci, tap) element of a layer belongs to exactly one tile, so the optimiser step of all
 // packed layers and their re-pack are ONE pass over the masters (the stand-alone re-pack read the 68 MB Adam had just written again).
-// The update is a compile-time policy of the load loop: PackNone (plain pack, and the no_update entries of an Adam launch), PackAdam,
-// PackAdamWd (weight_decay != 0, the `weight_parameters()` group of Train_Stage1_K.py:177-180).  The two Adam forms differ in the gradient
-// they feed the moments and keep their own arithmetic: the undecayed one is NOT the decayed one at decay = 0 (f32 product vs one rounding
-// of a double fma), and it is the benchmarked step.
+// The update is a compile-time policy of the load loop: PackNone (plain pack, and the no_update entries of an Adam launch), PackAdam<AdamGrad>,
+// PackAdam<AdamGradL2> (weight_decay != 0, the `weight_parameters()` group of Train_Stage1_K.py:177-180).  The two Adam forms differ in the
+// gradient they feed the moments and keep their own arithmetic: the undecayed one is NOT the decayed one at decay = 0 (f32 product vs one
+// rounding of a double fma), and it is the benchmarked step.
 struct PackNone {};
+template <typename Grad>
 struct PackAdam {
+    AdamCoef c;
+    Grad grad;
     int64_t g_off, m_off, v_off;  // element offsets from a master weight to its gradient / first / second moment (the flat buffers share one layout)
-    float b1, b2, eps, grad_scale, step_size, rsqrt_bc2;
-    __device__ __forceinline__ float grad(float, float g) const { return g * grad_scale; }
-};
-struct PackAdamWd : PackAdam {
-    double decay;  // gr is formed in double and rounded once (losses.hip: decayed_grad -- where g and decay * w cancel, an f32 sum would not do)
-    __device__ __forceinline__ float grad(float w, float g) const { return (float)fma(decay, (double)w, (double)g * (double)grad_scale); }
 };
 template <typename T, int TAPS, typename Update = PackNone>
 __device__ __forceinline__ void pack_tile(const falnet_pack_t& d, int rel, float (&tile)[32][32 * 9 + 1], const Update* ad = nullptr) {
@@ -40,10 +38,11 @@ __device__ __forceinline__ void pack_tile(const falnet_pack_t& d, int rel, float
             float* wp = const_cast<float*>(d.w) + ((int64_t)co * d.cin + ci0) * TAPS + k;
             val = *wp;
             if constexpr (!std::is_same<Update, PackNone>::value) {
-                const float gr = ad->grad(val, wp[ad->g_off]);
-                const float m = ad->b1 * wp[ad->m_off] + (1.f - ad->b1) * gr;
-                const float v = ad->b2 * wp[ad->v_off] + (1.f - ad->b2) * gr * gr;
-                val -= ad->step_size * m / (sqrtf(v) * ad->rsqrt_bc2 + ad->eps);
+                const float g = wp[ad->g_off];
+                // v before m on purpose: the order of these loads decides which of the two multiplies of the first moment the compiler fuses
+                // into its add, i.e. the bits of m (tools/isa_identity.py against the parent commit shows a change)
+                float v = wp[ad->v_off], m = wp[ad->m_off];
+                adam_update(ad->c, ad->grad, val, g, m, v);
                 *wp = val;
                 wp[ad->m_off] = m;
                 wp[ad->v_off] = v;
@@ -105,21 +104,14 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const falnet_
 
 // The optimiser step of every packed layer fused with its re-pack; ONE decay per launch is enough: every packed layer is a convolution
 // WEIGHT (biases are never packed; they and the unpacked weights go through falnet_adam_ranges[_wd] with a decay per range).
-template <typename T, typename Update>
-__device__ __forceinline__ void adam_pack_batched_body(Update ad, const falnet_pack_t* __restrict__ descs, int n, int64_t g_off, int64_t m_off, int64_t v_off,
+template <typename T, typename Grad>
+__device__ __forceinline__ void adam_pack_batched_body(Grad grad, const falnet_pack_t* __restrict__ descs, int n, int64_t g_off, int64_t m_off, int64_t v_off,
                                                        const float* __restrict__ state, float b1, float b2, float eps, float grad_scale,
                                                        const float* __restrict__ scaler) {
     __shared__ float tile[32][32 * 9 + 1];
     __shared__ int entry_begin[64];
-    if (scaler != nullptr) {
-        if (scaler[2] != 0.f) return;  // non-finite gradient somewhere: the whole update (decay included) is skipped, the packed copies stay valid (grid-uniform)
-        grad_scale /= scaler[0];
-    }
-    const float t = state[1] + 1.0f;
-    ad.g_off = g_off, ad.m_off = m_off, ad.v_off = v_off;
-    ad.b1 = b1, ad.b2 = b2, ad.eps = eps, ad.grad_scale = grad_scale;
-    ad.step_size = state[0] / (1.0f - powf(b1, t));
-    ad.rsqrt_bc2 = rsqrtf(1.0f - powf(b2, t));
+    PackAdam<Grad> ad{{}, grad, g_off, m_off, v_off};
+    if (!adam_begin(ad.c, state, b1, b2, eps, grad_scale, scaler)) return;  // a skipped step leaves the packed copies valid (grid-uniform)
     const int li = find_entry(descs, n, entry_begin);
     const falnet_pack_t d = descs[li];
     const int rel = blockIdx.x - d.block_begin;
@@ -136,16 +128,14 @@ template <typename T>
 __global__ __launch_bounds__(256) void adam_pack_batched_kernel(const falnet_pack_t* __restrict__ descs, int n, int64_t g_off, int64_t m_off, int64_t v_off,
                                                                 const float* __restrict__ state, float b1, float b2, float eps, float grad_scale,
                                                                 const float* __restrict__ scaler) {
-    adam_pack_batched_body<T>(PackAdam(), descs, n, g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler);
+    adam_pack_batched_body<T>(AdamGrad(), descs, n, g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void adam_pack_batched_wd_kernel(const falnet_pack_t* __restrict__ descs, int n, int64_t g_off, int64_t m_off, int64_t v_off,
                                                                    const float* __restrict__ state, float b1, float b2, float eps, float grad_scale,
                                                                    double decay, const float* __restrict__ scaler) {
-    PackAdamWd ad;
-    ad.decay = decay;
-    adam_pack_batched_body<T>(ad, descs, n, g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler);
+    adam_pack_batched_body<T>(AdamGradL2{decay}, descs, n, g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler);
 }
 
 // Sub-pixel weights of the deconv layers (conv_dma.hip: conv3x3_up2_dma_kernel): wu[co][pair][ci], pair = 4 (2 py + px) + 2 a + b

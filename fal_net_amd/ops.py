@@ -253,20 +253,27 @@ def conv_c3_call(dtype, x_planar, pc, out, act, name="conv0(c3)"):
     return call
 
 
-def pack_all_call(pcs, dtype, device):
-    """ONE launch that re-packs every layer's f32 OIHW master weight into its wf / wd operands."""
-    lib = L.lib()
+def _pack_table(pcs, n_own, device):
+    """The falnet_pack_t table of a batched pack launch on the device and its block count; entries from `n_own` on are no_update (only
+    packed by an Adam launch)."""
     descs = (L.PackDesc * len(pcs))()
     blk = 0
     for i, pc in enumerate(pcs):
+        descs[i].no_update = int(i >= n_own)
         c0_real, c0_pad = pc.group_channels()
         d = descs[i]
         d.w, d.wf, d.wd = pc.weight.data_ptr(), pc.wf.data_ptr(), pc.wd.data_ptr()
         d.cout, d.cin, d.taps, d.c0_real, d.c0_pad, d.cin_pad, d.cout_pad, d.block_begin = (
             pc.cout, pc.cin, pc.taps, c0_real, c0_pad, pc.cin_pad, pc.cout_pad, blk)
         blk += (pc.cout_pad // 32) * (pc.cin_pad // 32)
-    dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device)
-    n, total, code = len(pcs), blk, L.dtype_code(dtype)
+    return torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device), blk
+
+
+def pack_all_call(pcs, dtype, device):
+    """ONE launch that re-packs every layer's f32 OIHW master weight into its wf / wd operands."""
+    lib = L.lib()
+    dev, total = _pack_table(pcs, len(pcs), device)
+    n, code = len(pcs), L.dtype_code(dtype)
 
     def launch(_keep=(dev, pcs)):
         L.check(lib.falnet_pack_weights_batched(L.ptr(dev), n, total, code, L.stream_ptr()), "pack_weights_batched")
@@ -281,18 +288,8 @@ def adam_pack_call(pcs, dtype, device, derived=()):
     lib = L.lib()
     n_own = len(pcs)
     pcs = list(pcs) + list(derived)
-    descs = (L.PackDesc * len(pcs))()
-    blk = 0
-    for i, pc in enumerate(pcs):
-        descs[i].no_update = int(i >= n_own)
-        c0_real, c0_pad = pc.group_channels()
-        d = descs[i]
-        d.w, d.wf, d.wd = pc.weight.data_ptr(), pc.wf.data_ptr(), pc.wd.data_ptr()
-        d.cout, d.cin, d.taps, d.c0_real, d.c0_pad, d.cin_pad, d.cout_pad, d.block_begin = (
-            pc.cout, pc.cin, pc.taps, c0_real, c0_pad, pc.cin_pad, pc.cout_pad, blk)
-        blk += (pc.cout_pad // 32) * (pc.cin_pad // 32)
-    dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(device)
-    n, total, code = len(pcs), blk, L.dtype_code(dtype)
+    dev, total = _pack_table(pcs, n_own, device)
+    n, code = len(pcs), L.dtype_code(dtype)
 
     def launch(g_off, m_off, v_off, state, b1, b2, eps, grad_scale, scaler, weight_decay=0.0, _keep=(dev, pcs)):
         if weight_decay:

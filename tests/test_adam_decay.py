@@ -107,7 +107,7 @@ def test_bound_holds_for_f32_adam_and_sees_the_decay():
 
 
 def test_f32_decayed_gradient_leaves_the_bound_at_scale_and_the_double_form_does_not():
-    """Why the kernels form g + decay * p in double (csrc/losses.hip: decayed_grad) and the decays travel as doubles: 2 M elements, one step,
+    """Why the kernels form g + decay * p in double (csrc/adam.h: AdamGradL2) and the decays travel as doubles: 2 M elements, one step,
     gradients spread over several decades.  At the few elements per million where g and decay * p cancel, |gr| falls towards eps while an f32
     sum carries an error of 2^-24 |g|, and the first step lr * gr / (|gr| + eps) amplifies it by lr / eps: torch's own f32 Adam lands
     outside the float64 bound (about 10 x here); the kernels' arithmetic -- restated in torch f32 with gr formed in double and rounded
@@ -123,7 +123,7 @@ def test_f32_decayed_gradient_leaves_the_bound_at_scale_and_the_double_form_does
     p32.grad = grad.clone()
     torch.optim.Adam([p32], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd).step()
     r32 = float(((p32.detach().double() - want).abs() / R.bound(want, 1, lr)).max())
-    gr = (grad.double() + wd * p0.double()).float()  # decayed_grad(): one rounding
+    gr = (grad.double() + wd * p0.double()).float()  # AdamGradL2: one rounding
     m, v = (1 - b1) * gr, (1 - b2) * gr * gr
     step_size, rsqrt_bc2 = torch.tensor(lr / (1 - b1), dtype=torch.float32), torch.tensor((1 - b2) ** -0.5, dtype=torch.float32)
     dev = p0 - step_size * m / (v.sqrt() * rsqrt_bc2 + eps)

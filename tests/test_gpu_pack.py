@@ -433,6 +433,101 @@ def test_adam_pack_step_by_step(dtype, decay, gs, scaler, rows):
             assert torch.equal(s, t), f"{what}: a skipped step wrote something"
 
 
+# The pairs of (a) pack-fused, (b) range and (c) flat kernel that give an element the same bits, by bool(decay): measured, not designed.  The
+# kernels share one update (csrc/adam.h), but the compiler fuses multiplies into adds per kernel: the decayed range and flat kernels come
+# out alike, every other pair differs in the last place of v (and of a few p) -- figures in the test's docstring.
+PATHS_THAT_AGREE = {True: ("bc",), False: ()}
+
+
+@pytest.mark.parametrize("t0", [0, 6])
+@pytest.mark.parametrize("gs,scaler", [(1.0, None), (0.125, [4.0, 0.0, 0.0, 0.0])], ids=["unscaled", "scaled"])
+@pytest.mark.parametrize("decay", [0.0, 1e-2])
+def test_adam_paths_agree_bit_for_bit(decay, gs, scaler, t0):
+    """One FlatAdam.step() sends a weight through the pack-fused kernel, a bias through the range kernel and, without a plan or under stream
+    capture, the same parameters through the flat kernel: an element must get the same bits whichever path updates it (csrc/adam.h holds the
+    one update they all call).  Three copies of one (p, g, m, v) buffer -- the masters of adam_layout(), zeros in the gaps because the flat
+    kernel walks them -- take two consecutive steps each, (a) falnet_adam_pack_batched[_wd], (b) falnet_adam_ranges[_wd] with one range per
+    master, (c) falnet_adam_step_dev / _guarded / _wd over the whole row; p, m and v are compared as int32.  falnet_adam_step is no part of
+    it: it forms its coefficients on the host in double.
+    Measured on MI355X, the same before and after the update moved into adam.h (94 402 elements, two steps): decayed, (b) and (c) agree in
+    every bit, (a) differs from both in v on 12 448 .. 38 280 elements by <= 3 ulp, in p on <= 30 by <= 32 ulp (values near 0), in m on <= 1
+    by 1 ulp; undecayed, every pair differs: v on 5 .. 38 382 elements by <= 3 ulp, p on <= 50 by <= 2 ulp, m nowhere.  So only (b) == (c)
+    of the decayed form is asserted (PATHS_THAT_AGREE); every figure is printed (run with -s)."""
+    lib = L.lib()
+    K = 2
+    spans, n_flat = adam_layout()
+    host = torch.zeros(4, n_flat)  # rows p, g, m, v
+    real = torch.zeros(n_flat, dtype=torch.bool)
+    masters = {}
+    for name in ADAM_CASES:
+        off, n = spans[name]
+        real[off:off + n] = True
+        masters[name] = R.master(R.BY_NAME[name], "normal", BF16, seed=30)
+        host[0, off:off + n] = masters[name].reshape(-1)
+    if t0:  # moments as a run that is t0 steps old would hold them
+        host[2][real] = 0.5 * hand_gradient(n_flat, 7)[real]
+        host[3][real] = hand_gradient(n_flat, 8)[real] ** 2
+    bufs = {k: host.to(DEV) for k in "abc"}
+    states = {k: torch.tensor([LR, float(t0)], device=DEV) for k in "abc"}
+    sc = None if scaler is None else torch.tensor(scaler, device=DEV)
+    g_off, m_off, v_off = n_flat, 2 * n_flat, 3 * n_flat
+    entries = []
+    for name in ADAM_CASES:
+        e = Entry(R.BY_NAME[name], BF16, "normal", w=masters[name])
+        e.w_ptr = bufs["a"].data_ptr() + 4 * spans[name][0]
+        entries.append(e)
+    table, total = desc_table(entries)
+    ranges = torch.tensor([x for name in ADAM_CASES for x in spans[name]], dtype=torch.int64, device=DEV)
+    decays = torch.full((len(ADAM_CASES),), decay, dtype=torch.float64, device=DEV)
+    seg_end = torch.tensor([n_flat], dtype=torch.int64, device=DEV)
+    hyper = (BETAS[0], BETAS[1], EPS, gs)
+    st = L.stream_ptr()
+    for k in range(K):
+        g = torch.where(real, hand_gradient(n_flat, k), torch.zeros(n_flat)).to(DEV)
+        for b in bufs.values():
+            b[1].copy_(g)
+        a, r, c = bufs["a"], bufs["b"], bufs["c"]
+        if decay:
+            L.check(lib.falnet_adam_pack_batched_wd(L.ptr(table), len(entries), total, L.BF16, g_off, m_off, v_off, L.ptr(states["a"]), *hyper, decay,
+                                                    L.ptr(sc), st), "adam_pack_batched_wd")
+            L.check(lib.falnet_adam_ranges_wd(L.ptr(r), g_off, m_off, v_off, L.ptr(ranges), L.ptr(decays), len(ADAM_CASES), L.ptr(states["b"]), *hyper,
+                                              L.ptr(sc), st), "adam_ranges_wd")
+            L.check(lib.falnet_adam_step_wd(L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), n_flat, L.ptr(seg_end), L.ptr(decays), 1,
+                                            L.ptr(states["c"]), *hyper, L.ptr(sc), st), "adam_step_wd")
+        else:
+            L.check(lib.falnet_adam_pack_batched(L.ptr(table), len(entries), total, L.BF16, g_off, m_off, v_off, L.ptr(states["a"]), *hyper, L.ptr(sc), st),
+                    "adam_pack_batched")
+            L.check(lib.falnet_adam_ranges(L.ptr(r), g_off, m_off, v_off, L.ptr(ranges), len(ADAM_CASES), L.ptr(states["b"]), *hyper, L.ptr(sc), st),
+                    "adam_ranges")
+            if sc is None:
+                L.check(lib.falnet_adam_step_dev(L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), n_flat, L.ptr(states["c"]), *hyper, st), "adam_step_dev")
+            else:
+                L.check(lib.falnet_adam_step_guarded(L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), n_flat, L.ptr(states["c"]), *hyper, L.ptr(sc), st),
+                        "adam_step_guarded")
+        for k2 in "ab":  # (step_dev / _guarded / _wd tick their state themselves)
+            L.check(lib.falnet_adam_tick(L.ptr(states[k2]), L.ptr(sc), st), "adam_tick")
+    torch.cuda.synchronize()
+    got = {k: b.cpu().view(torch.int32) for k, b in bufs.items()}
+    what = f"adam paths decay={decay} gs={gs} scaler={scaler is not None} t0={t0}"
+
+    def ordered(bits):  # int32 view -> integers in the order of the floats: a difference of two is a distance in ulps
+        b = bits.to(torch.int64)
+        return torch.where(b < 0, -(b & 0x7fffffff), b)
+
+    differ = {}
+    for x, y in ("ab", "ac", "bc"):
+        for i, ch in ((0, "p"), (2, "m"), (3, "v")):
+            d = (ordered(got[x][i][real]) - ordered(got[y][i][real])).abs()
+            differ[f"{x}{y} {ch}"] = (int((d != 0).sum()), int(d.max()))
+    print(f"{what}: {int(real.sum())} elements, {K} steps; (elements that differ, most ulps) between (a) pack, (b) ranges, (c) flat: {differ}")
+    assert all(float(s[1]) == t0 + K for s in states.values()), states
+    assert not torch.equal(got["a"][0][real], host[0].view(torch.int32)[real])  # (the steps moved the weights)
+    for pair in (PATHS_THAT_AGREE[bool(decay)]):
+        assert not any(n for key, (n, _) in differ.items() if key.startswith(pair)), (what, pair, differ)
+    for i, ch in ((0, "p"), (2, "m"), (3, "v")):
+        assert not got["c"][i][~real].any(), f"{what}: the flat kernel left a gap of row {ch} other than +0"
+
+
 # ------------------------------------------------------------------------------------------------------------------ the model's own tables
 def check_model_operands(m, what):
     seen = {"wf": 0, "wu": 0, "wdd": 0, "taps": set()}
