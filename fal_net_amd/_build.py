@@ -23,8 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # order for the same reason (its threshold counts are compared with numpy's as integers).  augment_batch.hip restates the host's float64
 # resampling coefficients (data_transforms.resample_coeffs) for the same reason: its 22-bit integers must equal the host's.  velo.hip
 # restates the host's float64 projection sums in a fixed order: the pixel a point lands on must be the host's; lidar.hip, its inverse, restates
-# the host's float64 back-projection and bin search the same way: a record and its bin must be the host's bit for bit.  sparsify.hip restates
-# the depth chain of metrics.hip per pixel: its errors order the pixels and its d1 counts are compared with numpy's as integers.
+# the host's float64 back-projection and bin search the same way: a record and its bin must be the host's bit for bit.  sparsify.hip runs
+# the depth chain of metrics.hip per pixel (csrc/depth_pair.h, whose includers all need the flag): its errors order the pixels and its d1 counts
+# are compared with numpy's as integers.
 FILE_FLAGS = {"med_head.hip": ["-fno-slp-vectorize"], "med_head2.hip": ["-fno-slp-vectorize"], "med_sweep.hip": ["-fno-slp-vectorize"],
               "med_stats.hip": ["-fno-slp-vectorize"],
               "dump.hip": ["-ffp-contract=off"],
@@ -60,7 +61,7 @@ def build_ab(tag="ab", defines=(), verbose=True, raw=()):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "ordered.h"), os.path.join(CSRC, "depth_pair.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
     jobs = []
     for src in SOURCES:
         path = os.path.join(CSRC, src)

@@ -2,15 +2,18 @@
 //
 // Three launches, no atomics, nothing decides a position but the index:
 //   1  compact_count_kernel    workgroup g counts the kept records of its CP_TILE consecutive indices          -> ws[g]
-//   2  compact_scan_kernel     ONE workgroup turns the counts into exclusive offsets in place, 256 at a time    -> ws[g], *count
-//   3  compact_scatter_kernel  workgroup g evaluates its flags again, ranks them (ballot + popcount inside a wave, the wave totals through LDS,
-//                              a running base over the CP_ROUNDS rounds) and copies record i to dst[ws[g] + rank]
+//   2  offset_scan_kernel      ONE workgroup turns the counts into exclusive offsets in place, 256 at a time    -> ws[g], *count
+//   3  compact_scatter_kernel  workgroup g evaluates its flags again, ranks them (block_rank: ballot + popcount inside a wave, the wave totals
+//                              through LDS; a running base over the CP_ROUNDS rounds) and copies record i to dst[ws[g] + rank]
 // Records are 4 bytes (one word) or 15 bytes (a packed PLY vertex, unaligned: copied byte by byte).  dst beyond the kept records is not written.
+// The tile, block_count and block_rank are ordered.h's; the scan kernel is the only one of the library: lidar.hip and sparsify.hip reach it
+// through falnet_offset_scan, defined here.
 #include "common.h"
+#include "ordered.h"
 
-#define CP_THREADS 256
-#define CP_ROUNDS 8
-#define CP_TILE (CP_THREADS * CP_ROUNDS)
+#define CP_THREADS ORD_THREADS
+#define CP_ROUNDS ORD_ROUNDS
+#define CP_TILE ORD_TILE
 
 __device__ __forceinline__ bool compact_keep(const float* __restrict__ score, float threshold, int64_t i, int64_t n) {
     return i < n && score[i] >= threshold;
@@ -23,14 +26,12 @@ __global__ __launch_bounds__(CP_THREADS) void compact_count_kernel(const float* 
     int c = 0;
 #pragma unroll
     for (int r = 0; r < CP_ROUNDS; ++r) c += compact_keep(score, threshold, base + r * CP_THREADS + threadIdx.x, n) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) ws[blockIdx.x] = (int64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    const int total = block_count(c, wsum);
+    if (threadIdx.x == 0) ws[blockIdx.x] = (int64_t)total;
 }
 
-__global__ __launch_bounds__(CP_THREADS) void compact_scan_kernel(int64_t* __restrict__ ws, int64_t nblocks, int64_t* __restrict__ count) {
+// 256 counts at a time: an inclusive scan in LDS, and a carried base from one 256 to the next
+__global__ __launch_bounds__(CP_THREADS) void offset_scan_kernel(int64_t* __restrict__ ws, int64_t nblocks, int64_t* __restrict__ count) {
     __shared__ int64_t sh[CP_THREADS];
     __shared__ int64_t carry;
     if (threadIdx.x == 0) carry = 0;
@@ -55,30 +56,24 @@ __global__ __launch_bounds__(CP_THREADS) void compact_scan_kernel(int64_t* __res
     if (threadIdx.x == 0) *count = carry;
 }
 
+void falnet_offset_scan(int64_t* counts, int64_t nblocks, int64_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(offset_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, counts, nblocks, total);
+}
+
 template <int REC>
 __global__ __launch_bounds__(CP_THREADS) void compact_scatter_kernel(const unsigned char* __restrict__ src, const float* __restrict__ score,
                                                                      float threshold, int64_t n, unsigned char* __restrict__ dst,
                                                                      const int64_t* __restrict__ ws) {
     __shared__ int wsum[CP_THREADS / 64];
     const int64_t base = (int64_t)blockIdx.x * CP_TILE;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int64_t pos = ws[blockIdx.x];
     for (int r = 0; r < CP_ROUNDS; ++r) {
         const int64_t i = base + r * CP_THREADS + threadIdx.x;
         const bool keep = compact_keep(score, threshold, i, n);
-        const unsigned long long mask = __ballot(keep);
-        const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-        __syncthreads();  // the previous round's totals are read
-        if (lane == 0) wsum[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < CP_THREADS / 64; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
+        int total;
+        const int rank = block_rank(keep, wsum, total);
         if (keep) {
-            const int64_t j = pos + before + rank;
+            const int64_t j = pos + rank;
             if (REC == 4) {
                 reinterpret_cast<uint32_t*>(dst)[j] = reinterpret_cast<const uint32_t*>(src)[i];
             } else {
@@ -109,7 +104,7 @@ extern "C" int falnet_compact_records(const void* src, int rec_bytes, const floa
     int64_t* ws = static_cast<int64_t*>(workspace);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(CP_THREADS), 0, st, score, threshold, n, ws);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, ws, nb, count_dev);
+    falnet_offset_scan(ws, nb, count_dev, st);
     if (rec_bytes == 4)
         hipLaunchKernelGGL(compact_scatter_kernel<4>, dim3((unsigned)nb), dim3(CP_THREADS), 0, st, static_cast<const unsigned char*>(src), score, threshold, n,
                            static_cast<unsigned char*>(dst), ws);

@@ -9,9 +9,11 @@
 //     whatever pixels / channels they belong to.  The caller rounds the allocation up to a multiple of 4 bytes; the pad bytes are written 0.
 // None of this is on the training step's path and none of it is part of the autotune key (ops.py: _TUNE_SOURCES).
 #include "common.h"
+#include "ordered.h"
 
 // ---- exact percentile: radix select over the monotone integer image of the floats -----------------------------------------------------
-// key(x) is monotone in x (negative floats: all bits flipped; others: sign bit set), so the k-th smallest float is the k-th smallest key.
+// key_f32(x) (ordered.h) is monotone in x (negative floats: all bits flipped; others: sign bit set), so the k-th smallest float is the k-th
+// smallest key.
 // Four passes of 8 bits, most significant first.  A pass histograms the next byte of every element whose higher bytes equal the prefix found
 // so far (LDS histogram per workgroup, then integer atomics into the sample's 256-bin table: integer sums, so the result does not depend on
 // arrival order), and a one-workgroup kernel per sample walks the table to the bin that holds the wanted rank.  TWO ranks are tracked at once
@@ -21,12 +23,6 @@
 // [4] [5] the two order statistics as f32 (valid after the call), [6] [7] unused, then 4 passes x 2 slots x 256 bins.
 #define PCT_STATE 8
 #define PCT_WORDS (PCT_STATE + 4 * 2 * 256)
-
-__device__ __forceinline__ uint32_t pct_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float pct_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 __global__ __launch_bounds__(256) void percentile_hist_kernel(const float* __restrict__ x, uint32_t n, uint32_t* ws, int pass) {
     __shared__ uint32_t hist[2][256];
@@ -40,7 +36,7 @@ __global__ __launch_bounds__(256) void percentile_hist_kernel(const float* __res
     const uint32_t p0 = all ? 0 : w[0], p1 = all ? 0 : w[1];
     const float* xs = x + (size_t)blockIdx.y * n;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        const uint32_t k = pct_key(xs[i]);
+        const uint32_t k = key_f32(xs[i]);
         const uint32_t hi = all ? 0 : (k >> (shift + 8)), bin = (k >> shift) & 255u;
         if (hi == p0) atomicAdd(&hist[0][bin], 1u);
         if (hi == p1) atomicAdd(&hist[1][bin], 1u);
@@ -70,7 +66,7 @@ __global__ __launch_bounds__(128) void percentile_select_kernel(uint32_t* ws, in
         w[slot] = prefix;
         w[2 + slot] = rank;
         if (pass == 3) {
-            stat[slot] = pct_unkey(prefix);
+            stat[slot] = unkey_f32(prefix);
             w[4 + slot] = __float_as_uint(stat[slot]);
         }
     }

@@ -10,18 +10,20 @@
 // Three rules hold:
 //   * every + - * / and sqrt of steps 1, 4 and of the bin search is a correctly rounded operation in exactly this order: the file is compiled
 //     with -ffp-contract=off, so a point's record and its bin are the host's, bit for bit;
-//   * positions are decided by indices alone: a count pass, one scan and a scatter pass that evaluates the same predicate again (the
-//     launch shape of compact.hip), so the output order is the pixel (or bin) order and no intermediate record array exists;
+//   * positions are decided by indices alone: a count pass, the offset scan of compact.hip and a scatter pass that evaluates the same
+//     predicate again (the ordered compaction of ordered.h), so the output order is the pixel (or bin) order and no intermediate record
+//     array exists;
 //   * the only atomic is an integer atomicMin on a u64 key, whose result does not depend on arrival order: no floating-point atomics, and the
 //     output is bit-identical from run to run.
 // The all-ones sentinel of the key table is no pixel's key: its upper half is the pattern of a NaN, and a kept d has passed step 2.
 // Not on the training step's path, not replayable, and not part of the autotune key (ops.py: _TUNE_SOURCES).
 #include <math.h>
 #include "common.h"
+#include "ordered.h"
 
-#define LD_THREADS 256
-#define LD_ROUNDS 8
-#define LD_TILE (LD_THREADS * LD_ROUNDS)
+#define LD_THREADS ORD_THREADS
+#define LD_ROUNDS ORD_ROUNDS
+#define LD_TILE ORD_TILE
 #define LD_EMPTY 0xffffffffffffffffull
 #define LD_MAX_BEAMS 128
 #define LD_MAX_AZ 4096
@@ -117,64 +119,25 @@ __global__ __launch_bounds__(LD_THREADS) void lidar_count_kernel(LidarArgs a, co
         if (BEAM) c += (i < n && table[i] != LD_EMPTY) ? 1 : 0;
         else c += lidar_item<false>(a, table, i, n, rec) ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    const int total = block_count(c, wsum);
+    if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)total;
 }
 
-// ONE workgroup: the per-workgroup counts become exclusive offsets in place, 256 at a time; *count: the total
-__global__ __launch_bounds__(LD_THREADS) void lidar_scan_kernel(int64_t* __restrict__ counts, int nblocks, int64_t* __restrict__ count) {
-    __shared__ int64_t sh[LD_THREADS];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int g0 = 0; g0 < nblocks; g0 += LD_THREADS) {
-        const int g = g0 + threadIdx.x;
-        const int64_t v = g < nblocks ? counts[g] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < LD_THREADS; o <<= 1) {  // inclusive scan of the 256 counts
-            const int64_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int64_t before = carry;
-        if (g < nblocks) counts[g] = before + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == LD_THREADS - 1) carry = before + sh[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
-// the predicate again, ranked (ballot + popcount inside a wave, the wave totals through LDS, a running base over the rounds); record j of the
-// output is one 16-byte store, and only below `capacity`
+// the predicate again, ranked (block_rank, and a running base over the rounds); record j of the output is one 16-byte store, and only below
+// `capacity`
 template <bool BEAM>
 __global__ __launch_bounds__(LD_THREADS) void lidar_scatter_kernel(LidarArgs a, const unsigned long long* __restrict__ table, uint32_t n,
                                                                    const int64_t* __restrict__ offsets, float4* __restrict__ out, int64_t capacity) {
     __shared__ int wsum[LD_THREADS / 64];
     const uint32_t base = blockIdx.x * LD_TILE;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int64_t pos = offsets[blockIdx.x];
     for (int r = 0; r < LD_ROUNDS; ++r) {
         float4 rec;
         const bool keep = lidar_item<BEAM>(a, table, base + r * LD_THREADS + threadIdx.x, n, rec);
-        const unsigned long long mask = __ballot(keep);
-        const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-        __syncthreads();  // the previous round's totals are read
-        if (lane == 0) wsum[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < LD_THREADS / 64; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
+        int total;
+        const int rank = block_rank(keep, wsum, total);
         if (keep) {
-            const int64_t j = pos + before + rank;
+            const int64_t j = pos + rank;
             if (j < capacity) out[j] = rec;
         }
         pos += total;
@@ -229,7 +192,7 @@ extern "C" int falnet_velo_unproject(const float* map, double fb, const float* s
         int64_t* counts = static_cast<int64_t*>(workspace);
         const int nb = (int)lidar_blocks(a.n);
         hipLaunchKernelGGL(lidar_count_kernel<false>, dim3(nb), threads, 0, st, a, (const unsigned long long*)nullptr, a.n, counts);
-        hipLaunchKernelGGL(lidar_scan_kernel, dim3(1), threads, 0, st, counts, nb, count_dev);
+        falnet_offset_scan(counts, nb, count_dev, st);
         hipLaunchKernelGGL(lidar_scatter_kernel<false>, dim3(nb), threads, 0, st, a, (const unsigned long long*)nullptr, a.n, counts, out, capacity);
     } else {
         const uint32_t bins = (uint32_t)beams * (uint32_t)az_bins;
@@ -239,7 +202,7 @@ extern "C" int falnet_velo_unproject(const float* map, double fb, const float* s
         hipLaunchKernelGGL(lidar_fill_kernel, dim3((bins + LD_THREADS - 1) / LD_THREADS), threads, 0, st, table, bins);
         hipLaunchKernelGGL(lidar_key_kernel, dim3((a.n + LD_THREADS - 1) / LD_THREADS), threads, 0, st, a, beams, az_bins, elev_edges_dev, az_edges_dev, table);
         hipLaunchKernelGGL(lidar_count_kernel<true>, dim3(nb), threads, 0, st, a, table, bins, counts);
-        hipLaunchKernelGGL(lidar_scan_kernel, dim3(1), threads, 0, st, counts, nb, count_dev);
+        falnet_offset_scan(counts, nb, count_dev, st);
         hipLaunchKernelGGL(lidar_scatter_kernel<true>, dim3(nb), threads, 0, st, a, table, bins, counts, out, capacity);
     }
     FALNET_RETURN_LAUNCH();

@@ -4,18 +4,21 @@
 // reads the table once after its last frame instead of copying two full-size maps to the host per frame.
 //
 // Three rules hold throughout:
-//   * the depth chain is f64 per pixel in the HOST's order (the host chain is float64 because `1.0 - mask` promotes it; the `< 1.25^n` counts
-//     are discontinuous, so f32 arithmetic would flip pixels near a threshold).  This file is compiled with -ffp-contract=off: no fused
-//     multiply-add, correctly rounded f64 division and square root.  One thing the host does in f32 is done in f32 here too: the Eigen /
-//     Make3D ground truth stays an f32 array on the host, so np.median of it takes the mean of the two middle values in f32 (the scale factor
-//     is compared at 1e-14).  The host's np.log of that f32 array is an f32 logarithm as well; the kernel takes the f64 one, the correctly
-//     rounded value of which the host's is a rounding (measured closer to the host than the device's own logf, which rounds differently);
+//   * the depth chain (depth_pair.h, shared with sparsify.hip) is f64 per pixel in the HOST's order (the host chain is float64 because `1.0 -
+//     mask` promotes it; the `< 1.25^n` counts are discontinuous, so f32 arithmetic would flip pixels near a threshold).  This file is compiled
+//     with -ffp-contract=off: no fused multiply-add, correctly rounded f64 division and square root.  One thing the host does in f32 is done in
+//     f32 here too: the Eigen / Make3D ground truth stays an f32 array on the host, so np.median of it takes the mean of the two middle values
+//     in f32 (the scale factor is compared at 1e-14).  The host's np.log of that f32 array is an f32 logarithm as well; the kernel takes the f64
+//     one, the correctly rounded value of which the host's is a rounding (measured closer to the host than the device's own logf, which rounds
+//     differently);
 //   * every reduction is deterministic by construction: a FIXED grid of MET_BLOCKS workgroups writes one line of partial sums each (wave
 //     shuffles, then the four waves in order), and a finalising kernel adds the lines in index order.  No floating-point atomics; the
 //     radix select counts with integer atomics, whose sums do not depend on arrival order;
 //   * nothing is read by the host: the median scale factor goes from the select to the error kernel through device memory.
 // None of this is on the training step's path and none of it is part of the autotune key (ops.py: _TUNE_SOURCES).
 #include "common.h"
+#include "depth_pair.h"
+#include "ordered.h"
 
 #define MET_BLOCKS 256
 #define MET_THREADS 256
@@ -30,12 +33,6 @@
 extern "C" int64_t falnet_metrics_workspace_bytes(void) { return (int64_t)MET_WS_WORDS64 * 8; }
 
 // ---- block reduction: NS doubles per thread -> one line of partial sums per workgroup ------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int NS> __device__ __forceinline__ void store_partials(double (&v)[NS], double* __restrict__ partials) {
     __shared__ double red[MET_THREADS / 64][NS];
 #pragma unroll
@@ -54,43 +51,13 @@ template <int NS> __device__ __forceinline__ void store_partials(double (&v)[NS]
     }
 }
 
-// ---- depth pairs ---------------------------------------------------------------------------------------------------------------------------
-struct DepthArgs {
-    const float* pred;  // predicted disparity, H x W
-    const float* gt;    // ground truth, H x W: a disparity (kitti2015) or a depth (eigen, make3d)
-    int W, y0, x0, rh, rw;  // row pitch and the region that counts (the Eigen crop, or the whole frame)
-    int mode;
-    double fb;     // focal * baseline, formed by the caller exactly as the host chain forms it
-    double max_d;  // make3d: the mask is 0 < gt < max_d
-};
-
-// pixel i of the region -> (gt depth, predicted depth) in f64 as the host forms them; false where the ground truth is masked out.
-//   kitti2015: depth = fb / (d + (1 - [d > 0])) for both maps; eigen / make3d: gt is a depth already.  A prediction <= 0 takes the d + 1 denominator.
-__device__ __forceinline__ bool depth_pair(const DepthArgs& a, uint32_t i, double& g, double& p) {
-    const uint32_t r = i / (uint32_t)a.rw, c = i - r * (uint32_t)a.rw;
-    const size_t idx = (size_t)(a.y0 + r) * a.W + (a.x0 + c);
-    const float gf = a.gt[idx];
-    if (!(gf > 0.f)) return false;
-    if (a.mode == FALNET_DEPTH_MAKE3D && !((double)gf < a.max_d)) return false;
-    const float pf = a.pred[idx];
-    p = a.fb / ((double)pf + (1.0 - (pf > 0.f ? 1.0 : 0.0)));
-    g = a.mode == FALNET_DEPTH_KITTI2015 ? a.fb / ((double)gf + (1.0 - 1.0)) : (double)gf;
-    return true;
-}
-
 // ---- np.median of gt[mask] and pred[mask] on the device -------------------------------------------------------------------------------------
-// A radix select (the scheme of dump.hip's percentile) over the f64 DEPTHS themselves, with a predicate (mask and crop) and a 64-bit key: eight
-// passes of 8 bits.  The alternative -- selecting on the f32 disparities and converting the two order statistics afterwards -- is exact only
+// A radix select (the scheme of dump.hip's percentile) over the f64 DEPTHS themselves, with a predicate (mask and crop) and a 64-bit key
+// (key_f64 of ordered.h): eight passes of 8 bits.  The alternative -- selecting on the f32 disparities and converting the two order statistics afterwards -- is exact only
 // where the depth is monotone in the stored value, and the prediction's is not: a disparity <= 0 takes the denominator d + 1, an f64 that
 // need not be an f32, and a negative denominator gives a negative depth that sorts below every positive one.  Selecting the values numpy sorts
 // needs no such case analysis.  The number of selected pixels is the sum of the first pass's histogram; the ranks (n - 1) / 2 and n / 2 follow
 // from it on the device.
-__device__ __forceinline__ uint64_t med_key(double v) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double med_unkey(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k)); }
-
 __global__ __launch_bounds__(MET_THREADS) void median_hist_kernel(DepthArgs a, uint64_t* __restrict__ state, uint32_t* __restrict__ tables, int pass) {
     __shared__ uint32_t hist[MED_SLOTS][256];
     for (int s = 0; s < MED_SLOTS; ++s) hist[s][threadIdx.x] = 0;
@@ -104,7 +71,7 @@ __global__ __launch_bounds__(MET_THREADS) void median_hist_kernel(DepthArgs a, u
     for (uint32_t i = blockIdx.x * MET_THREADS + threadIdx.x; i < n; i += gridDim.x * MET_THREADS) {
         double g, p;
         if (!depth_pair(a, i, g, p)) continue;
-        const uint64_t kg = med_key(g), kp = med_key(p);
+        const uint64_t kg = key_f64(g), kp = key_f64(p);
         const uint64_t hg = all ? 0 : (kg >> (shift + 8)), hp = all ? 0 : (kp >> (shift + 8));
         const uint32_t bg = (uint32_t)(kg >> shift) & 255u, bp = (uint32_t)(kp >> shift) & 255u;
         if (hg == pre[0]) atomicAdd(&hist[0][bg], 1u);
@@ -147,7 +114,7 @@ __global__ __launch_bounds__(256) void median_select_kernel(uint64_t* __restrict
         state[slot] = prefix;
         state[4 + slot] = rank;
         if (pass == MED_PASSES - 1) {
-            stat[slot] = med_unkey(prefix);
+            stat[slot] = unkey_f64(prefix);
             state[9 + slot] = (uint64_t)__double_as_longlong(stat[slot]);
         }
     }
@@ -178,10 +145,7 @@ __global__ __launch_bounds__(MET_THREADS) void depth_errors_kernel(DepthArgs a, 
     for (uint32_t i = blockIdx.x * MET_THREADS + threadIdx.x; i < n; i += gridDim.x * MET_THREADS) {
         double g, p;
         if (!depth_pair(a, i, g, p)) continue;
-        if (scaled) p = factor * p;
-        p = fmin(fmax(p, min_d), max_d);
-        g = fmin(fmax(g, min_d), max_d);
-        const double t = fmax(g / p, p / g);
+        const double t = depth_scale_clamp(g, p, scaled, factor, min_d, max_d);
         cn += 1;
         c1 += t < 1.25 ? 1u : 0u;
         c2 += t < 1.5625 ? 1u : 0u;    // 1.25 ** 2, exact
@@ -287,21 +251,6 @@ __global__ __launch_bounds__(64) void metrics_finalize_kernel(const double* __re
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------------------
-static int depth_args(DepthArgs& a, const float* pred, const float* gt, int H, int W, int mode, double fb, double max_d, const char* who) {
-    FALNET_CHECK_ARG(pred && gt, "%s: null map", who);
-    FALNET_CHECK_ARG(mode == FALNET_DEPTH_KITTI2015 || mode == FALNET_DEPTH_EIGEN || mode == FALNET_DEPTH_MAKE3D,
-                     "%s: unknown mode %d (0 kitti2015, 1 eigen, 2 make3d)", who, mode);
-    FALNET_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: frame %d x %d must hold between 1 and 2^31 pixels", who, H, W);
-    FALNET_CHECK_ARG(fb > 0.0, "%s: focal * baseline must be positive", who);
-    a.pred = pred, a.gt = gt, a.W = W, a.mode = mode, a.fb = fb, a.max_d = max_d;
-    a.y0 = 0, a.x0 = 0, a.rh = H, a.rw = W;
-    if (mode == FALNET_DEPTH_EIGEN) {  // rows H - 219 : H - 4, columns 44 : 1180 (myUtils.py:256-277)
-        FALNET_CHECK_ARG(H >= 219 && W >= 1180, "%s: frame %d x %d is smaller than the Eigen crop (rows H - 219 : H - 4, columns 44 : 1180)", who, H, W);
-        a.y0 = H - 219, a.x0 = 44, a.rh = 215, a.rw = 1136;
-    }
-    return 0;
-}
-
 static inline double* ws_partials(void* ws) { return (double*)ws; }
 static inline uint64_t* ws_state(void* ws) { return (uint64_t*)ws + MET_BLOCKS * MET_NSUM; }
 static inline uint32_t* ws_tables(void* ws) { return (uint32_t*)((uint64_t*)ws + MET_BLOCKS * MET_NSUM + MED_STATE); }

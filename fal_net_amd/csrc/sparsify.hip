@@ -3,54 +3,30 @@
 // abs_rel, rms and d1 = 1 - a1 of the pixels that are left are written for `steps` cuts into one row of doubles.
 //
 //   1  sp_count_kernel     workgroup g counts the pixels of its SP_TILE consecutive region positions that depth_pair accepts     -> counts[g]
-//   2  sp_scan_kernel      ONE workgroup: exclusive offsets in place, 256 at a time with a carried base                          -> counts[g], *n
-//   3  sp_scatter_kernel   the ordered compaction of compact.hip: counted pixel number k (region row-major order) gets its errors e_abs[k],
+//   2  falnet_offset_scan  the offset scan of compact.hip: exclusive offsets in place                                             -> counts[g], *n
+//   3  sp_scatter_kernel   the ordered compaction of ordered.h: counted pixel number k (region row-major order) gets its errors e_abs[k],
 //                          e_sq[k], the flag t < 1.25 and one sort key per ordering, keys[s * N + k]
 //   4  falnet_sort_u32     all orderings in one call over N = the region's size: the positions n .. N - 1, which hold no pixel, keep the key
 //                          0xFFFFFFFF of the pre-fill, above every key a value can have, so the first n ranks are the counted pixels
 //   5  sp_interval_kernel  workgroup (j, s) sums the errors of ordering s over the ranks r_j .. r_(j+1) - 1 that cut j + 1 removes beyond cut j
 //   6  sp_finalize_kernel  thread s adds the interval sums from the last cut to the first and writes the curves
-// The depth chain is metrics.hip's, f64 in the host's order, and this file is compiled with -ffp-contract=off for the same reason.  Every sum
+// The depth chain is depth_pair.h's, the one of metrics.hip, f64 in the host's order: this file is compiled with -ffp-contract=off.  Every sum
 // has a fixed partition and a fixed order (a thread's stride, the shuffles of a wave, the four waves in order, the intervals in order): two calls
 // give the same bits.  No floating-point atomics, no atomics at all.  The number of counted pixels never leaves the device.
 #include "common.h"
+#include "depth_pair.h"
+#include "ordered.h"
 
-#define SP_THREADS 256
-#define SP_ROUNDS 8
-#define SP_TILE (SP_THREADS * SP_ROUNDS)
+#define SP_THREADS ORD_THREADS
+#define SP_ROUNDS ORD_ROUNDS
+#define SP_TILE ORD_TILE
 #define SP_MAX_STEPS 100
 #define SP_MAX_SCORES 4
 #define SP_MAX_PIXELS (1ll << 24)
 
-// ---- depth pairs: a copy of metrics.hip's ----------------------------------------------------------------------------------------------------
-struct DepthArgs {
-    const float* pred;  // predicted disparity, H x W
-    const float* gt;    // ground truth, H x W: a disparity (kitti2015) or a depth (eigen, make3d)
-    int W, y0, x0, rh, rw;  // row pitch and the region that counts (the Eigen crop, or the whole frame)
-    int mode;
-    double fb;     // focal * baseline, formed by the caller exactly as the host chain forms it
-    double max_d;  // make3d: the mask is 0 < gt < max_d
-};
-
-// pixel i of the region -> (gt depth, predicted depth) in f64 as the host forms them; false where the ground truth is masked out.
-__device__ __forceinline__ bool depth_pair(const DepthArgs& a, uint32_t i, double& g, double& p, size_t& idx) {
-    const uint32_t r = i / (uint32_t)a.rw, c = i - r * (uint32_t)a.rw;
-    idx = (size_t)(a.y0 + r) * a.W + (a.x0 + c);
-    const float gf = a.gt[idx];
-    if (!(gf > 0.f)) return false;
-    if (a.mode == FALNET_DEPTH_MAKE3D && !((double)gf < a.max_d)) return false;
-    const float pf = a.pred[idx];
-    p = a.fb / ((double)pf + (1.0 - (pf > 0.f ? 1.0 : 0.0)));
-    g = a.mode == FALNET_DEPTH_KITTI2015 ? a.fb / ((double)gf + (1.0 - 1.0)) : (double)gf;
-    return true;
-}
-
-// the monotone image of an f32 (-0 below +0, NaN above everything), complemented: an ascending sort removes the most uncertain pixel first
-__device__ __forceinline__ uint32_t sort_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    const uint32_t k = x != x ? 0xFFFFFFFFu : ((u >> 31) ? (u ^ 0xFFFFFFFFu) : (u | 0x80000000u));
-    return ~k;
-}
+// the monotone image of an f32 (-0 below +0) with every NaN above everything, complemented: an ascending sort removes the most uncertain pixel
+// first
+__device__ __forceinline__ uint32_t sort_key(float x) { return ~(x != x ? 0xFFFFFFFFu : key_f32(x)); }
 
 // ---- the numbering of the counted pixels ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SP_THREADS) void sp_count_kernel(DepthArgs a, uint32_t N, int64_t* __restrict__ counts) {
@@ -64,36 +40,8 @@ __global__ __launch_bounds__(SP_THREADS) void sp_count_kernel(DepthArgs a, uint3
         size_t idx;
         c += i < N && depth_pair(a, i, g, p, idx) ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-}
-
-__global__ __launch_bounds__(SP_THREADS) void sp_scan_kernel(int64_t* __restrict__ counts, int64_t nblocks, int64_t* __restrict__ total) {
-    __shared__ int64_t sh[SP_THREADS];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t g0 = 0; g0 < nblocks; g0 += SP_THREADS) {
-        const int64_t g = g0 + threadIdx.x;
-        const int64_t v = g < nblocks ? counts[g] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < SP_THREADS; o <<= 1) {  // inclusive scan of the 256 counts
-            const int64_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int64_t before = carry;
-        if (g < nblocks) counts[g] = before + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == SP_THREADS - 1) carry = before + sh[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+    const int total = block_count(c, wsum);
+    if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)total;
 }
 
 struct SpBuffers {
@@ -107,7 +55,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_scatter_kernel(DepthArgs a, uin
                                                                 falnet_scores_t sc, const int64_t* __restrict__ counts, SpBuffers o) {
     __shared__ int wsum[SP_THREADS / 64];
     const uint32_t base = blockIdx.x * SP_TILE;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool scaled = scale != nullptr;
     const double factor = scaled ? scale[0] : 1.0;
     uint32_t pos = (uint32_t)counts[blockIdx.x];
@@ -116,23 +63,11 @@ __global__ __launch_bounds__(SP_THREADS) void sp_scatter_kernel(DepthArgs a, uin
         double g = 1.0, p = 1.0;
         size_t idx = 0;
         const bool keep = i < N && depth_pair(a, i, g, p, idx);
-        const unsigned long long mask = __ballot(keep);
-        const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-        __syncthreads();  // the previous round's totals are read
-        if (lane == 0) wsum[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < SP_THREADS / 64; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
+        int total;
+        const int rank = block_rank(keep, wsum, total);
         if (keep) {
-            const uint32_t k = pos + before + rank;  // < n <= N
-            if (scaled) p = factor * p;
-            p = fmin(fmax(p, min_d), max_d);
-            g = fmin(fmax(g, min_d), max_d);
-            const double t = fmax(g / p, p / g);
+            const uint32_t k = pos + rank;  // < n <= N
+            const double t = depth_scale_clamp(g, p, scaled, factor, min_d, max_d);
             const double d = g - p;
             const double e_abs = fabs(d) / g, e_sq = d * d;
             o.e_abs[k] = e_abs;
@@ -158,12 +93,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_scatter_kernel(DepthArgs a, uin
 // cut j removes the first r_j = (j n) / S ranks
 __device__ __forceinline__ uint32_t cut_rank(uint32_t j, uint32_t n, uint32_t S) { return (uint32_t)(((uint64_t)j * n) / S); }
 
-__device__ __forceinline__ double sp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // workgroup (j, s): the sums of ordering s over the ranks [r_j, r_(j+1)) -- the last interval ends at n -> partial[(s * S + j) * 3 + {abs, sq, count}].
 // An oracle ordering sums its own metric only (the two other entries are written 0 and never read).
 __global__ __launch_bounds__(SP_THREADS) void sp_interval_kernel(const uint32_t* __restrict__ perm, uint32_t N, const int64_t* __restrict__ total, int n_scores,
@@ -182,7 +111,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_interval_kernel(const uint32_t*
         if (own < 0 || own == 2) c += o.lt[k];
     }
     double v2 = (double)c;
-    v0 = sp_wave_sum(v0), v1 = sp_wave_sum(v1), v2 = sp_wave_sum(v2);
+    v0 = wave_sum_f64(v0), v1 = wave_sum_f64(v1), v2 = wave_sum_f64(v2);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) red[w][0] = v0, red[w][1] = v1, red[w][2] = v2;
     __syncthreads();
@@ -247,11 +176,10 @@ extern "C" int64_t falnet_sparsify_workspace_bytes(int H, int W, int n_scores) {
 extern "C" int falnet_sparsify(const float* pred_disp, const float* gt, int H, int W, int mode, double fb, const double* scale, double min_d, double max_d,
                                falnet_scores_t scores, int steps, double* row, void* workspace, void* stream) {
     FALNET_ENTER(stream);
-    FALNET_CHECK_ARG(pred_disp && gt, "sparsify: null map");
-    FALNET_CHECK_ARG(mode == FALNET_DEPTH_KITTI2015 || mode == FALNET_DEPTH_EIGEN || mode == FALNET_DEPTH_MAKE3D,
-                     "sparsify: unknown mode %d (0 kitti2015, 1 eigen, 2 make3d)", mode);
+    // the sort's cap first: the shared checks speak of the 2^31 pixels of the metrics
     FALNET_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W <= SP_MAX_PIXELS, "sparsify: frame %d x %d must hold between 1 and 2^24 pixels", H, W);
-    FALNET_CHECK_ARG(fb > 0.0, "sparsify: focal * baseline must be positive");
+    DepthArgs a;
+    if (depth_args(a, pred_disp, gt, H, W, mode, fb, max_d, "sparsify")) return -1;
     FALNET_CHECK_ARG(steps >= 2 && steps <= SP_MAX_STEPS, "sparsify: steps=%d outside [2, %d]", steps, SP_MAX_STEPS);
     FALNET_CHECK_ARG(scores.n >= 0 && scores.n <= SP_MAX_SCORES, "sparsify: %d scores (0 to %d)", scores.n, SP_MAX_SCORES);
     for (int s = 0; s < scores.n; ++s) {
@@ -264,13 +192,6 @@ extern "C" int falnet_sparsify(const float* pred_disp, const float* gt, int H, i
                      "sparsify: workspace, row and scale must be 8-byte aligned");
     FALNET_CHECK_ARG(min_d > 0.0 && max_d >= min_d, "sparsify: need 0 < min_d <= max_d");
     FALNET_CHECK_ARG(mode != FALNET_DEPTH_MAKE3D || scale, "sparsify: make3d is always median-scaled (scale from falnet_depth_median_scale)");
-    DepthArgs a;
-    a.pred = pred_disp, a.gt = gt, a.W = W, a.mode = mode, a.fb = fb, a.max_d = max_d;
-    a.y0 = 0, a.x0 = 0, a.rh = H, a.rw = W;
-    if (mode == FALNET_DEPTH_EIGEN) {  // rows H - 219 : H - 4, columns 44 : 1180
-        FALNET_CHECK_ARG(H >= 219 && W >= 1180, "sparsify: frame %d x %d is smaller than the Eigen crop (rows H - 219 : H - 4, columns 44 : 1180)", H, W);
-        a.y0 = H - 219, a.x0 = 44, a.rh = 215, a.rw = 1136;
-    }
     const int64_t N = (int64_t)a.rh * a.rw;
     const int seg = scores.n + 3;
     const SpLayout l = sp_layout((int64_t)H * W, scores.n);
@@ -290,7 +211,7 @@ extern "C" int falnet_sparsify(const float* pred_disp, const float* gt, int H, i
     }
     const unsigned tiles = (unsigned)sp_tiles(N);
     hipLaunchKernelGGL(sp_count_kernel, dim3(tiles), dim3(SP_THREADS), 0, st, a, (uint32_t)N, counts);
-    hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(SP_THREADS), 0, st, counts, (int64_t)tiles, total);
+    falnet_offset_scan(counts, (int64_t)tiles, total, st);
     hipLaunchKernelGGL(sp_scatter_kernel, dim3(tiles), dim3(SP_THREADS), 0, st, a, (uint32_t)N, scale, min_d, max_d, scores, (const int64_t*)counts, o);
     const int rc = falnet_sort_u32(o.keys, N, seg, perm, ws + l.sort, stream);
     if (rc != 0) return rc;

@@ -10,14 +10,15 @@
 // Two rules hold:
 //   * every + and * of step 2 and both divisions are correctly rounded f64 operations in exactly this order: this file is compiled with
 //     -ffp-contract=off (no fused multiply-add), so the pixel a point lands on -- a discontinuous function of s -- is the one the host chain finds;
-//   * the z-buffer is an integer atomicMin on the monotone 32-bit image of the f32 depth (the mapping of dump.hip's pct_key; a copy, dump.hip
-//     is not touched).  An integer minimum does not depend on arrival order: the map is bit-identical for any order of the points and from run
+//   * the z-buffer is an integer atomicMin on the monotone 32-bit image of the f32 depth (key_f32 of ordered.h, the key of dump.hip's
+//     percentile).  An integer minimum does not depend on arrival order: the map is bit-identical for any order of the points and from run
 //     to run.  No floating-point atomics.  Rounding to f32 is monotone, so the minimum of the rounded depths is the rounded minimum.
 // The all-ones sentinel of the fill pass is the key of a positive NaN only; a landed point's depth is never NaN (a NaN s_2 fails step 5, and
 // with vel_depth x >= 0 has passed step 1).
 // Not on the training step's path, not replayable, and not part of the autotune key (ops.py: _TUNE_SOURCES).
 #include <math.h>
 #include "common.h"
+#include "ordered.h"
 
 #define VELO_THREADS 256
 #define VELO_EMPTY 0xffffffffu
@@ -25,12 +26,6 @@
 struct VeloP {
     double m[12];  // row-major 3 x 4, by value in the kernel arguments
 };
-
-__device__ __forceinline__ uint32_t velo_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float velo_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
 __global__ __launch_bounds__(VELO_THREADS) void velo_fill_kernel(uint32_t* __restrict__ keys, uint32_t n) {
     const uint32_t i = blockIdx.x * VELO_THREADS + threadIdx.x;
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(VELO_THREADS) void velo_scatter_kernel(const float*
     const double u = rint(s0 / s2) - 1.0, v = rint(s1 / s2) - 1.0;
     if (!(u >= 0.0 && v >= 0.0 && u < (double)W && v < (double)H)) return;
     const float d = vel_depth ? xf : (float)s2;
-    atomicMin(&keys[(size_t)(int)v * W + (int)u], velo_key(d));  // 0 <= v < H, 0 <= u < W hold as doubles: the index is inside the map
+    atomicMin(&keys[(size_t)(int)v * W + (int)u], key_f32(d));  // 0 <= v < H, 0 <= u < W hold as doubles: the index is inside the map
 }
 
 // keys -> depths in place: the sentinel and every value that is not positive become 0
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(VELO_THREADS) void velo_finish_kernel(uint32_t* __r
     const uint32_t i = blockIdx.x * VELO_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint32_t k = keys[i];
-    const float d = velo_unkey(k);
+    const float d = unkey_f32(k);
     keys[i] = (k != VELO_EMPTY && d > 0.f) ? __float_as_uint(d) : 0u;
 }
 

@@ -205,11 +205,13 @@ def raw_compact(rec, score, thr):
     return rc, dst.cpu().numpy(), int(count.item())
 
 
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 2048, 2049, 65537])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 2048, 2049, 65537, 256 * 2048, 256 * 2048 + 1, 2 * 256 * 2048 + 2049])
 @pytest.mark.parametrize("rec_bytes", [4, 15])
 def test_compaction_against_numpy(n, rec_bytes):
     """dst[:count] and count equal numpy's boolean indexing byte for byte, the bytes beyond keep their pre-fill; kept fraction 0, 1 and about
-    a half, NaN scores present.  (2048 and 2049: one workgroup's tile of csrc/compact.hip and one record more, beside the issue's sizes.)"""
+    a half, NaN scores present.  (2048 and 2049: one workgroup's tile of csrc/compact.hip and one record more, beside the issue's sizes.
+    The offset scan takes 256 workgroup counts at a time and carries a base: 256 * 2048 records are exactly one such chunk, one record more
+    puts a single workgroup with a single record into a second chunk, and the last size needs three.)"""
     rec = S.make_records(n, rec_bytes)
     for kind in ("none", "all", "half"):
         score = S.make_scores(n, kind)

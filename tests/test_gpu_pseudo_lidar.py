@@ -26,6 +26,8 @@ INF = float("inf")
 # H, W, scale of the first two rows of P.  13 x 7: one partial wave; 37 x 124: 4588 pixels, three workgroup tiles of 2048 with a partial last one;
 # 375 x 1242: 228 tiles, the native KITTI frame
 SIZES = {"13x7": (13, 7, 0.01), "37x124": (37, 124, 0.1), "375x1242": (375, 1242, 1.0)}
+# 513 x 1025: 525 825 pixels, 257 tiles -- one more than the offset scan takes at a time, so its carried base decides the last tile's offset
+CARRY_SIZE = {"513x1025": (513, 1025, 1.0)}
 GUARD_ROWS = 64
 GUARD_WORD = 0x5A5AA5A5  # as f32 a large finite number no record holds
 
@@ -33,7 +35,7 @@ GUARD_WORD = 0x5A5AA5A5  # as f32 a large finite number no record holds
 @functools.lru_cache(maxsize=None)
 def frame(name):
     """The inputs of one size, computed once per session and left unchanged: P, fb, the road-like depth, its disparity, a score and an intensity map."""
-    H, W, scale = SIZES[name]
+    H, W, scale = {**SIZES, **CARRY_SIZE}[name]
     rng = np.random.default_rng(17)
     P, depth = R.kitti_like_P(scale), LR.road_depth(3, H, W)
     fb = 721.5377 * scale * 0.54
@@ -96,6 +98,17 @@ def test_dense_equals_reference(name, form, max_height):
     assert sizes[0] == sizes[1] > sizes[2] == sizes[3] > 0  # the score drops about half; the intensity map changes no count
     if max_height == INF and form == "depth":
         assert sizes[0] == int((f["depth"] > 0).sum()) >= len(reference(name, form, False, False, 1.0))
+
+
+def test_dense_past_one_chunk_of_tile_counts():
+    """257 tiles: the records of the last tile sit behind the total of the first 256, which only the scan's second round hands on."""
+    name = "513x1025"
+    f = frame(name)
+    want = reference(name, "depth", True, True, 1.0)
+    check(f["depth"], f["P"], want, f"{name} depth score=True intensity map=True max_height=1.0", score=f["score"], threshold=0.5, intensity=f["inten"],
+          max_height=1.0)
+    idx = LR.kept_records(f["depth"], f["P"], None, f["score"], 0.5, f["inten"], 0.0, 80.0, 1.0)[0]
+    assert len(idx) == len(want) and 0 < int((idx >= 256 * 2048).sum()) < len(idx)  # kept pixels on both sides of the 257th tile's first pixel
 
 
 # ---- beam mode ----------------------------------------------------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ GUARD = 64
 def small_widths(monkeypatch):
     """The camera tables of myUtils know KITTI widths only; the small frames take the 1242-pixel camera scaled to their width -- on both sides,
     which read the same dictionaries."""
-    for w in (7, 124):
+    for w in (7, 124, 1025):
         monkeypatch.setitem(utils.width_to_focal, w, 721.5377 * w / 1242)
         monkeypatch.setitem(utils.width_to_baseline, w, 0.9982 * 0.54)
 
@@ -134,6 +134,8 @@ CASES = {  # mode, H, W, valid fraction, scores, median, steps
     "375x1242-eigen-dense-median": ("eigen", 375, 1242, 1.0, ("special",), True, 20),
     "375x1242-kitti2015-sparse-median": ("kitti2015", 375, 1242, 0.05, ALL, True, 50),
     "375x1242-kitti2015-third": ("kitti2015", 375, 1242, 0.3, ("noisy", "conf"), False, 50),
+    # 525 825 pixels: 257 tiles, one more than the offset scan takes at a time -- the last tile's pixels are numbered from the carried base
+    "513x1025-kitti2015-half": ("kitti2015", 513, 1025, 0.5, ("noisy", "conf"), False, 50),
 }
 
 

@@ -207,7 +207,13 @@ def test_entry_points_in_header_binding_and_build():
     assert "sort.hip" not in ops._TUNE_SOURCES and "sparsify.hip" not in ops._TUNE_SOURCES and _lib.EXPECTED_VERSION == 600
     sort_src = open(os.path.join(_build.CSRC, "sort.hip")).read()
     assert not re.search(r"\b(float|double)\b", re.sub(r"//.*", "", sort_src))  # no floating point in the sort
-    assert "metrics.hip" in _build.SOURCES and "depth_pair" in open(os.path.join(_build.CSRC, "sparsify.hip")).read()
+    # the depth chain is written once, in depth_pair.h, and every file that includes it is compiled without contraction
+    text = {f: open(os.path.join(_build.CSRC, f)).read() for f in sorted(os.listdir(_build.CSRC)) if f.endswith((".hip", ".h", ".cpp"))}
+    users = [f for f in _build.SOURCES if '#include "depth_pair.h"' in text[f]]
+    assert "sparsify.hip" in users and "metrics.hip" in users
+    assert [f for f in text if "struct DepthArgs" in text[f]] == ["depth_pair.h"]
+    assert all(_build.FILE_FLAGS.get(f) == ["-ffp-contract=off"] for f in users), users
+    assert "ordered.h" not in ops._TUNE_SOURCES and "depth_pair.h" not in ops._TUNE_SOURCES
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "fal_net_amd", "libfalnet_hip.so")), reason="library not built")

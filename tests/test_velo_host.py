@@ -193,4 +193,9 @@ def test_entry_point_in_header_binding_and_build():
     assert len(sig) == 8 and sig[-1] is _lib._P and sig[1] is _lib._I
     assert "velo.hip" in _build.SOURCES and _build.FILE_FLAGS["velo.hip"] == ["-ffp-contract=off"]
     assert "velo.hip" not in ops._TUNE_SOURCES and _lib.EXPECTED_VERSION == 600  # the packaged autotune cache stays valid
-    assert "velo_key" in open(os.path.join(_build.CSRC, "velo.hip")).read() and "velo" not in open(os.path.join(_build.CSRC, "dump.hip")).read()
+    # the monotone f32 key is written once, in ordered.h: neither file spells the mapping out
+    for name in ("velo.hip", "dump.hip"):
+        src = open(os.path.join(_build.CSRC, name)).read()
+        assert '#include "ordered.h"' in src and "key_f32(" in src and "0x80000000u" not in src, name
+    assert "0x80000000u" in open(os.path.join(_build.CSRC, "ordered.h")).read()
+    assert "ordered.h" not in ops._TUNE_SOURCES and "depth_pair.h" not in ops._TUNE_SOURCES
