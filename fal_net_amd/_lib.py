@@ -115,6 +115,9 @@ SIGNATURES = {
     "falnet_conv2d": [C.POINTER(Conv), _P],
     "falnet_conv3x3_c3": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "falnet_conv2d_multi": [C.POINTER(Conv), _I, _P],
+    "falnet_conv2d_wgs": [C.POINTER(Conv), _I, _P],
+    "falnet_conv2d_workgroups": [C.POINTER(Conv), _I],
+    "falnet_conv2d_multi_wgs": [C.POINTER(Conv), _I, _I, _P],
     "falnet_conv2d_kernel_name": [C.POINTER(Conv), C.c_char_p, _I],
     "falnet_wgrad_workspace_bytes": [C.POINTER(Wgrad)],
     "falnet_wgrad": [C.POINTER(Wgrad), _P],

@@ -50,6 +50,23 @@ static inline void falnet_enter_stream(void* stream) {
         return 0;                                                                \
     } while (0)
 
+// Grid width of a PERSISTENT conv launch (its kernel strides the tile loop by gridDim.x): `full` workgroups fill the chip (one or two per CU),
+// a workgroup budget max_wgs > 0 (falnet_conv2d_wgs) caps the launch's total at min(max_wgs, full); ny = output-channel blocks (gridDim.y).
+static inline int falnet_persistent_gx(int full, int ny, int ntiles, int max_wgs) {
+    int gx = (max_wgs > 0 && max_wgs < full ? max_wgs : full) / ny;
+    if (gx < 1) gx = 1;
+    if (gx > ntiles) gx = ntiles;
+    return gx;
+}
+// falnet_conv2d_workgroups: a launcher called with `count` set reports the workgroups it would launch and issues nothing (no device call)
+#define FALNET_COUNT_ONLY(count, n) \
+    do {                            \
+        if (count) {                \
+            *(count) = (n);         \
+            return 0;               \
+        }                           \
+    } while (0)
+
 typedef __bf16 bf16_t;
 typedef _Float16 f16_t;
 

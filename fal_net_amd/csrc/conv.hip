@@ -1614,6 +1614,8 @@ enum class ConvFamily {
 struct ConvChoice {
     ConvFamily family;
     int bn, kcb, tps, adb, th, nwaves, flip, swap;
+    int max_wgs;  // workgroup budget of a persistent launch (falnet_conv2d_wgs); 0 = the full grid.  The other families ignore it
+    int* count;   // falnet_conv2d_workgroups: the launcher reports its workgroup count here and launches nothing; nullptr = launch
 };
 
 // A/B switch for tests and profiling: FALNET_DISABLE_PATCH=1 routes every launch to the gather kernel
@@ -1623,27 +1625,29 @@ static int g_patch_kcb = [] { const char* e = falnet_ab_env("FALNET_PATCH_KCB");
 
 
 bool falnet_conv_dma_applicable(const falnet_conv_t& p, int min_oh);        // conv_dma.hip
-int falnet_conv_dma_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th);
+int falnet_conv_dma_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count);
 bool falnet_conv_dma2_applicable(const falnet_conv_t& p, int th);           // four rows per wave, 16-channel chunks: 16x32 tiles, two four-wave workgroups per CU (21) / 32x32 tiles, eight waves (22)
-int falnet_conv_dma2_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th);
-int falnet_conv_dma16_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th);  // variants 13 / 17 / 20 on v_mfma_f32_16x16x32 (variants 23 / 24 / 25)
+int falnet_conv_dma2_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count);
+int falnet_conv_dma16_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count);  // variants 13 / 17 / 20 on v_mfma_f32_16x16x32 (variants 23 / 24 / 25)
 bool falnet_conv_up2_dma_applicable(const falnet_conv_t& p);                // deconv forward in sub-pixel form (variant 18)
-int falnet_conv_up2_dma_launch(const falnet_conv_t& p, hipStream_t st);
+int falnet_conv_up2_dma_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count);
 bool falnet_conv_wave32_applicable(const falnet_conv_t& p);                 // conv_wave.hip: wave-streaming 32 -> 32 channel kernel (variant 27)
-int falnet_conv_wave32_launch(const falnet_conv_t& p, int flip, hipStream_t st);
+int falnet_conv_wave32_launch(const falnet_conv_t& p, int flip, hipStream_t st, int* count);
 bool falnet_conv_wave64p_applicable(const falnet_conv_t& p);                // conv_wave.hip: wave-streaming 64 -> (<= 4) channel kernel, planar f32 output (variant 29)
-int falnet_conv_wave64p_launch(const falnet_conv_t& p, int flip, hipStream_t st);
+int falnet_conv_wave64p_launch(const falnet_conv_t& p, int flip, hipStream_t st, int* count);
 bool falnet_conv_up2d_applicable(const falnet_conv_t& p);                   // deconv data gradient on the low-resolution grid (variant 26)
-int falnet_conv_up2d_launch(const falnet_conv_t& p, hipStream_t st);
+int falnet_conv_up2d_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count);
 bool falnet_conv_deep_applicable(const falnet_conv_t& p);                   // maps of <= 128 positions: one-shot LDS-DMA, K slices, last-arriver epilogue (variant 19)
-int falnet_conv_deep_launch(const falnet_conv_t& p, hipStream_t st);
+int falnet_conv_deep_launch(const falnet_conv_t& p, hipStream_t st, int* count);
 int falnet_conv_deep_mtiles(const falnet_conv_t& p);
 bool falnet_conv_s2d_dma_applicable(const falnet_conv_t* d, int n);         // four parity classes of a stride-2 data gradient in one pass
-int falnet_conv_s2d_dma_launch(const falnet_conv_t* d, hipStream_t st);
+int falnet_conv_s2d_dma_launch(const falnet_conv_t* d, hipStream_t st, int max_wgs, int* count);
 bool falnet_conv_s2f_dma_applicable(const falnet_conv_t& p);                // forward 3x3 stride-2
-int falnet_conv_s2f_dma_launch(const falnet_conv_t& p, hipStream_t st);
+int falnet_conv_s2f_dma_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count);
 
-static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c) {
+static int choose_conv_kernel(const falnet_conv_t& p, ConvChoice& c, int max_wgs = 0, int* count = nullptr) {
+    c.max_wgs = max_wgs;
+    c.count = count;
     const bool planar = p.out_layout == FALNET_OUT_PLANAR_F32;
     int ctot = 0;
     for (int s = 0; s < p.nsrc; ++s) ctot += p.src[s].C;
@@ -1876,6 +1880,7 @@ static int launch_gather(const falnet_conv_t& p, const ConvChoice& c, hipStream_
         // no memset: the workspace is zero on entry by contract (the epilogue kernel below re-zeroes what it consumes)
     }
     const dim3 grid((unsigned)((M + CONV_BM - 1) / CONV_BM), (unsigned)((p.Cout + bn - 1) / bn), (unsigned)ksplit);
+    FALNET_COUNT_ONLY(c.count, (int)(grid.x * grid.y * grid.z));
 #define GATHER_L(T)                                          \
     if (planar) launch_conv<T, true>(p, bn, grid, st);       \
     else launch_conv<T, false>(p, bn, grid, st);
@@ -1894,6 +1899,7 @@ static int launch_gather(const falnet_conv_t& p, const ConvChoice& c, hipStream_
 static int launch_patch(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st) {
     const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + c.th - 1) / c.th;
     const dim3 grid((unsigned)(p.B * tiles_x * tiles_y), (unsigned)((p.Cout + c.bn - 1) / c.bn));
+    FALNET_COUNT_ONLY(c.count, (int)(grid.x * grid.y));
     bool launched = false;
 #define TRY_PATCH(T, BN, KCB, TPS, ADB, TH, NW)                                                                              \
     if (!launched && c.bn == BN && c.kcb == KCB && c.tps == TPS && c.adb == (ADB ? 1 : 0) && c.th == TH) {                     \
@@ -1922,9 +1928,8 @@ static int launch_ws(const falnet_conv_t& p, const ConvChoice& c, hipStream_t st
     const int ws_th = c.th;
     const int tiles_x = (p.OW + PT_TW - 1) / PT_TW, tiles_y = (p.OH + ws_th - 1) / ws_th;
     const int ny = (p.Cout + c.bn - 1) / c.bn, ntiles = p.B * tiles_x * tiles_y;
-    int gx = 256 / ny;  // one persistent workgroup per CU (146 KB of LDS each)
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, c.max_wgs);  // one persistent workgroup per CU (146 KB of LDS each)
+    FALNET_COUNT_ONLY(c.count, gx * ny);
     const dim3 grid((unsigned)gx, (unsigned)ny);
     const bool m16 = falnet_mfma16_enabled();  // v_mfma_f32_16x16x32 form (16-bit types)
     const bool ws2_full = ws2_whole_lines(p);
@@ -1965,19 +1970,19 @@ static const ConvFamilyRow conv_families[] = {
     {ConvFamily::Gather, SYMBOL("_Z17conv_igemm_kernelI%sLi%dELb%dEEv13falnet_conv_t", t, c.bn, c.swap), launch_gather},
     {ConvFamily::Patch, SYMBOL("_Z20conv3x3_patch_kernelI%sLi%dELi%dELi%dELb%dELi%dELi%dEEv13falnet_conv_tiii", t, c.bn, c.kcb, c.tps, c.adb, c.th, c.nwaves), launch_patch},
     {ConvFamily::WeightStationary, ws_symbol, launch_ws},
-    {ConvFamily::Dma, SYMBOL("_Z18conv3x3_dma_kernelI%sLi%dELi%dEEv13falnet_conv_tiiii", t, c.th, c.nwaves), LAUNCH(falnet_conv_dma_launch(p, c.flip, st, c.th))},
-    {ConvFamily::S2fDma, SYMBOL("_Z22conv3x3_s2f_dma_kernelI%sLi%dEEv13falnet_conv_tiii", t, c.bn), LAUNCH(falnet_conv_s2f_dma_launch(p, st))},
-    {ConvFamily::Up2Dma, SYMBOL("_Z22conv3x3_up2_dma_kernelI%sEv13falnet_conv_tiiiii", t), LAUNCH(falnet_conv_up2_dma_launch(p, st))},
-    {ConvFamily::Deep, SYMBOL("_Z19conv3x3_deep_kernelI%sLi%dELi%dEEv13falnet_conv_t18falnet_deep_geom_t", t, c.kcb, c.nwaves), LAUNCH(falnet_conv_deep_launch(p, st))},
-    {ConvFamily::Dma2, SYMBOL("_Z19conv3x3_dma2_kernelI%sLb%dELi%dEEv13falnet_conv_tiiiii", t, p.pool_out ? 1 : 0, c.nwaves), LAUNCH(falnet_conv_dma2_launch(p, c.flip, st, c.th))},
+    {ConvFamily::Dma, SYMBOL("_Z18conv3x3_dma_kernelI%sLi%dELi%dEEv13falnet_conv_tiiii", t, c.th, c.nwaves), LAUNCH(falnet_conv_dma_launch(p, c.flip, st, c.th, c.max_wgs, c.count))},
+    {ConvFamily::S2fDma, SYMBOL("_Z22conv3x3_s2f_dma_kernelI%sLi%dEEv13falnet_conv_tiii", t, c.bn), LAUNCH(falnet_conv_s2f_dma_launch(p, st, c.max_wgs, c.count))},
+    {ConvFamily::Up2Dma, SYMBOL("_Z22conv3x3_up2_dma_kernelI%sEv13falnet_conv_tiiiii", t), LAUNCH(falnet_conv_up2_dma_launch(p, st, c.max_wgs, c.count))},
+    {ConvFamily::Deep, SYMBOL("_Z19conv3x3_deep_kernelI%sLi%dELi%dEEv13falnet_conv_t18falnet_deep_geom_t", t, c.kcb, c.nwaves), LAUNCH(falnet_conv_deep_launch(p, st, c.count))},
+    {ConvFamily::Dma2, SYMBOL("_Z19conv3x3_dma2_kernelI%sLb%dELi%dEEv13falnet_conv_tiiiii", t, p.pool_out ? 1 : 0, c.nwaves), LAUNCH(falnet_conv_dma2_launch(p, c.flip, st, c.th, c.max_wgs, c.count))},
     {ConvFamily::Dma16, [](char* buf, int len, const char* t, const falnet_conv_t& p, const ConvChoice& c) {
          if (p.pool_out && p.pool_code) return snprintf(buf, len, "_Z20conv3x3_dma16_kernelI9PoolCodesI%sELb1ELi16ELi8ELb0EEv13falnet_conv_tiiii", t);
          return snprintf(buf, len, "_Z20conv3x3_dma16_kernelI%sLb%dELi%dELi%dELb%dEEv13falnet_conv_tiiii", t, p.pool_out ? 1 : 0, c.th, c.nwaves, p.out_layout == FALNET_OUT_PLANAR_F32 ? 1 : 0);
      },
-     LAUNCH(falnet_conv_dma16_launch(p, c.flip, st, c.th))},
-    {ConvFamily::Up2d, SYMBOL("_Z25conv2x2_up2d_dma16_kernelI%sEv13falnet_conv_tiii", t), LAUNCH(falnet_conv_up2d_launch(p, st))},
-    {ConvFamily::Wave32, SYMBOL("_Z21conv3x3_wave32_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave32_launch(p, c.flip, st))},
-    {ConvFamily::Wave64p, SYMBOL("_Z22conv3x3_wave64p_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave64p_launch(p, c.flip, st))},
+     LAUNCH(falnet_conv_dma16_launch(p, c.flip, st, c.th, c.max_wgs, c.count))},
+    {ConvFamily::Up2d, SYMBOL("_Z25conv2x2_up2d_dma16_kernelI%sEv13falnet_conv_tiii", t), LAUNCH(falnet_conv_up2d_launch(p, st, c.max_wgs, c.count))},
+    {ConvFamily::Wave32, SYMBOL("_Z21conv3x3_wave32_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave32_launch(p, c.flip, st, c.count))},
+    {ConvFamily::Wave64p, SYMBOL("_Z22conv3x3_wave64p_kernelI%sEv13falnet_conv_tiiii", t), LAUNCH(falnet_conv_wave64p_launch(p, c.flip, st, c.count))},
 };
 #undef SYMBOL
 #undef LAUNCH
@@ -2001,9 +2006,10 @@ extern "C" int falnet_conv2d_kernel_name(const falnet_conv_t* pp, char* buf, int
     return 0;
 }
 
-extern "C" int falnet_conv2d(const falnet_conv_t* pp, void* stream) {
-    FALNET_ENTER(stream);
+// Argument checks of a conv launch, shared by falnet_conv2d_wgs and falnet_conv2d_workgroups (no device call)
+static int check_conv_desc(const falnet_conv_t* pp, int max_wgs) {
     FALNET_CHECK_ARG(pp, "conv2d: null descriptor");
+    FALNET_CHECK_ARG(max_wgs >= 0, "conv2d: workgroup budget %d (0 = the full grid, > 0 = at most that many workgroups)", max_wgs);
     const falnet_conv_t& p = *pp;
     FALNET_CHECK_ARG(p.dtype == FALNET_F32 || p.dtype == FALNET_BF16 || p.dtype == FALNET_F16, "conv2d: bad dtype %d", p.dtype);
     const int kc = p.dtype == FALNET_F32 ? 16 : 32;
@@ -2027,13 +2033,34 @@ extern "C" int falnet_conv2d(const falnet_conv_t* pp, void* stream) {
         falnet_set_error("conv2d: split-K (f32 atomics) is not available in deterministic mode");
         return -2;
     }
+    return 0;
+}
+
+extern "C" int falnet_conv2d_wgs(const falnet_conv_t* pp, int max_workgroups, void* stream) {
+    FALNET_ENTER(stream);
+    if (int r = check_conv_desc(pp, max_workgroups)) return r;
+    const falnet_conv_t& p = *pp;
     hipStream_t st = (hipStream_t)stream;
     ConvChoice c;
-    if (int r = choose_conv_kernel(p, c)) return r;
+    if (int r = choose_conv_kernel(p, c, max_workgroups)) return r;
     const ConvFamilyRow* row = conv_family_row(c.family);
     if (!row) return -1;
     if (int r = row->launch(p, c, st)) return r;
     FALNET_RETURN_LAUNCH();
+}
+
+extern "C" int falnet_conv2d(const falnet_conv_t* pp, void* stream) { return falnet_conv2d_wgs(pp, 0, stream); }
+
+// Workgroups falnet_conv2d_wgs(pp, max_workgroups, .) would launch: the same checks, choice and grid arithmetic, nothing issued.
+extern "C" int falnet_conv2d_workgroups(const falnet_conv_t* pp, int max_workgroups) {
+    if (int r = check_conv_desc(pp, max_workgroups)) return r < 0 ? r : -r;
+    ConvChoice c;
+    int n = 0;
+    if (int r = choose_conv_kernel(*pp, c, max_workgroups, &n)) return r < 0 ? r : -r;
+    const ConvFamilyRow* row = conv_family_row(c.family);
+    if (!row) return -1;
+    if (int r = row->launch(*pp, c, nullptr)) return r < 0 ? r : -r;
+    return n;
 }
 
 extern "C" int falnet_conv3x3_c3(const float* x_nchw, const float* w_oihw, const float* bias, void* out, int B, int H, int W, int Cout,
@@ -2064,15 +2091,18 @@ extern "C" int falnet_conv3x3_c3(const float* x_nchw, const float* w_oihw, const
     FALNET_RETURN_LAUNCH();
 }
 
-extern "C" int falnet_conv2d_multi(const falnet_conv_t* descs, int n, void* stream) {
+extern "C" int falnet_conv2d_multi(const falnet_conv_t* descs, int n, void* stream) { return falnet_conv2d_multi_wgs(descs, n, 0, stream); }
+
+extern "C" int falnet_conv2d_multi_wgs(const falnet_conv_t* descs, int n, int max_workgroups, void* stream) {
     FALNET_ENTER(stream);
     FALNET_CHECK_ARG(descs && n >= 1 && n <= 4, "conv2d_multi: 1..4 descriptors");
+    FALNET_CHECK_ARG(max_workgroups >= 0, "conv2d_multi: workgroup budget %d (0 = the full grid, > 0 = at most that many workgroups)", max_workgroups);
     if (descs[0].variant == 14) {  // fused LDS-DMA kernel for the canonical 3x3 stride-2 data gradient (conv_dma.hip)
         for (int i = 0; i < n; ++i)
             for (int s = 0; s < descs[i].nsrc && s < 2; ++s)
                 if (int r = check_src(descs[i].src[s], 32, "conv2d_multi")) return r;
         FALNET_CHECK_ARG(falnet_conv_s2d_dma_applicable(descs, n), "conv2d_multi: variant 14 needs the four parity classes of one 16-bit 3x3 stride-2 data gradient");
-        return falnet_conv_s2d_dma_launch(descs, (hipStream_t)stream);
+        return falnet_conv_s2d_dma_launch(descs, (hipStream_t)stream, max_workgroups, nullptr);
     }
     if (descs[0].ksplit > 1 && falnet_deterministic()) {
         falnet_set_error("conv2d_multi: split-K (f32 atomics) is not available in deterministic mode");

@@ -391,20 +391,23 @@ bool falnet_conv_dma_applicable(const falnet_conv_t& p, int min_oh) {
 // round idle) or 512 four-row tiles whose nine weight tiles (37 KB per 32-channel chunk) are staged for only 128 positions; eight-row tiles
 // are 256 x 4: every CU busy and 2x the positions per staged weight byte of the four-row form.
 template <typename T, int TH, int NWAVES>
-static void dma_launch_t(const falnet_conv_t& p, int flip, hipStream_t st) {
+static void dma_launch_t(const falnet_conv_t& p, int flip, hipStream_t st, int max_wgs, int* count) {
     const int tiles_x = (p.OW + 31) / 32, tiles_y = (p.OH + TH - 1) / TH;
     const int ntiles = p.B * tiles_x * tiles_y;
     const int ny = (p.Cout + 63) / 64;
-    int gx = 256 / ny;  // one persistent workgroup per CU
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);  // one persistent workgroup per CU
+    if (count) {
+        *count = gx * ny;
+        return;
+    }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_dma_kernel<T, TH, NWAVES>), dim3((unsigned)gx, (unsigned)ny), dim3(NWAVES * 64), 0, st, p, tiles_x, tiles_y, flip, ntiles);
 }
 
-int falnet_conv_dma_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th) {
-#define DMA_L(T) do { if (th == 4) dma_launch_t<T, 4, 4>(p, flip, st); else if (th == 8) dma_launch_t<T, 8, 8>(p, flip, st); else dma_launch_t<T, 16, 8>(p, flip, st); } while (0)
+int falnet_conv_dma_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count) {
+#define DMA_L(T) do { if (th == 4) dma_launch_t<T, 4, 4>(p, flip, st, max_wgs, count); else if (th == 8) dma_launch_t<T, 8, 8>(p, flip, st, max_wgs, count); else dma_launch_t<T, 16, 8>(p, flip, st, max_wgs, count); } while (0)
     FALNET_DISPATCH_16(p.dtype, DMA_L);
 #undef DMA_L
+    if (count) return 0;
     FALNET_RETURN_LAUNCH();
 }
 
@@ -640,14 +643,13 @@ bool falnet_conv_dma2_applicable(const falnet_conv_t& p, int th) {
     return falnet_conv_dma_applicable(p, th) && p.out_layout == FALNET_OUT_NHWC;
 }
 
-int falnet_conv_dma2_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th) {
+int falnet_conv_dma2_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count) {
     const int tiles_x = (p.OW + 31) / 32, tiles_y = (p.OH + th - 1) / th;
     const int ntiles = p.B * tiles_x * tiles_y;
     const int ny = (p.Cout + 63) / 64;
-    int gx = (th == 32 ? 256 : 512) / ny;  // one persistent eight-wave workgroup per CU, or two four-wave ones
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(th == 32 ? 256 : 512, ny, ntiles, max_wgs);  // one persistent eight-wave workgroup per CU, or two four-wave ones
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
     // start skew of the CUs' second residents: FALNET_DMA2_SKEW percent (experiment builds only; default 0) of a tile's time, taken as 5 200
     // cycles per 16-channel chunk; none when the grid has a single resident per CU.  Measured (profiles/r05_dma2_probes.txt): 25 % +-0, 50 % and
     // 100 % cost what they delay -- a workgroup alone on its CU does not run faster than beside its partner, so the two are not fighting over
@@ -987,14 +989,13 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 8 ? 2 : 1) void conv3x3_dma1
 #undef CD16_B
 }
 
-int falnet_conv_dma16_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th) {
+int falnet_conv_dma16_launch(const falnet_conv_t& p, int flip, hipStream_t st, int th, int max_wgs, int* count) {
     const int tiles_x = (p.OW + 31) / 32, tiles_y = (p.OH + th - 1) / th;
     const int ntiles = p.B * tiles_x * tiles_y;
     const int ny = (p.Cout + 63) / 64;
-    int gx = 256 / ny;  // one persistent workgroup per CU
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);  // one persistent workgroup per CU
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
     const bool planar = p.out_layout == FALNET_OUT_PLANAR_F32;
 #define DMA16_K(T, PL, TH_, NW, PN) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_dma16_kernel<T, PL, TH_, NW, PN>), grid, dim3(NW * 64), 0, st, p, tiles_x, tiles_y, flip, ntiles)
 #define DMA16_L(T)                                        \
@@ -1261,14 +1262,13 @@ bool falnet_conv_up2d_applicable(const falnet_conv_t& p) {
     return true;
 }
 
-int falnet_conv_up2d_launch(const falnet_conv_t& p, hipStream_t st) {
+int falnet_conv_up2d_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count) {
     const int tiles_x = (p.OW + 31) / 32, tiles_y = (p.OH + 15) / 16;
     const int ntiles = p.B * tiles_x * tiles_y;
     const int ny = (p.Cout + 63) / 64;
-    int gx = 256 / ny;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
     if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv2x2_up2d_dma16_kernel<f16_t>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv2x2_up2d_dma16_kernel<bf16_t>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles);
     FALNET_RETURN_LAUNCH();
@@ -1502,7 +1502,7 @@ bool falnet_conv_s2d_dma_applicable(const falnet_conv_t* d, int n) {
     return true;
 }
 
-int falnet_conv_s2d_dma_launch(const falnet_conv_t* d, hipStream_t st) {
+int falnet_conv_s2d_dma_launch(const falnet_conv_t* d, hipStream_t st, int max_wgs, int* count) {
     const falnet_conv_t& p = d[3];
     const int GH = p.IH, GW = p.IW;  // the upstream-gradient grid
     const int ny = (p.Cout + 31) / 32;
@@ -1513,10 +1513,9 @@ int falnet_conv_s2d_dma_launch(const falnet_conv_t* d, hipStream_t st) {
     const int th = small ? 8 : 16;
     const int tiles_y = (GH + th - 1) / th;
     const int ntiles = p.B * tiles_x * tiles_y;
-    int gx = 256 / ny;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
 #define S2D_L(T)                                                                                                                                     \
     do {                                                                                                                                             \
         if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_s2d_dma_kernel<T, 1>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles, GH, GW);  \
@@ -1723,15 +1722,14 @@ bool falnet_conv_up2_dma_applicable(const falnet_conv_t& p) {
     return true;
 }
 
-int falnet_conv_up2_dma_launch(const falnet_conv_t& p, hipStream_t st) {
+int falnet_conv_up2_dma_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count) {
     const int GH = p.src[0].H, GW = p.src[0].W;  // the low-resolution grid
     const int tiles_x = (GW + 31) / 32, tiles_y = (GH + 15) / 16;
     const int ntiles = p.B * tiles_x * tiles_y;
     const int ny = (p.Cout + 31) / 32;
-    int gx = 256 / ny;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
     if (p.dtype == FALNET_F16)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_up2_dma_kernel<f16_t>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles, GH, GW);
     else
@@ -2053,13 +2051,14 @@ int falnet_conv_deep_mtiles(const falnet_conv_t& p) {  // 4 or 8: the instantiat
     return mtw;
 }
 
-int falnet_conv_deep_launch(const falnet_conv_t& p, hipStream_t st) {
+int falnet_conv_deep_launch(const falnet_conv_t& p, hipStream_t st, int* count) {
     falnet_deep_geom_t g;
     int npl, mtw;
     size_t lds_bytes;
     deep_geometry(p, g, npl, mtw, lds_bytes);
     const int ntiles = g.mtiles * (p.w_rows / 64);
     const dim3 grid((unsigned)((ntiles + 7) / 8 * 8 * p.ksplit));
+    FALNET_COUNT_ONLY(count, (int)grid.x);
 #define DEEP_L(T) do {                                                          \
         if (npl == 1 && mtw == 4) deep_launch<T, 1, 4>(p, g, lds_bytes, grid, st);      \
         else if (npl == 1) deep_launch<T, 1, 8>(p, g, lds_bytes, grid, st);             \
@@ -2295,17 +2294,16 @@ bool falnet_conv_s2f_dma_applicable(const falnet_conv_t& p) {
     return true;
 }
 
-int falnet_conv_s2f_dma_launch(const falnet_conv_t& p, hipStream_t st) {
+int falnet_conv_s2f_dma_launch(const falnet_conv_t& p, hipStream_t st, int max_wgs, int* count) {
     const int tiles_x = (p.OW + 31) / 32, tiles_y = (p.OH + 7) / 8;
     const int ntiles = p.B * tiles_x * tiles_y;
     static const bool allow128 = [] { const char* e = falnet_ab_env("FALNET_S2F_BN128"); return e && e[0] == '1'; }();  // (128-channel form: 36-41 spilled VGPRs)
     const bool wide = allow128 && p.w_rows % 128 == 0 && p.Cout > 64;
     const int bn = wide ? 128 : 64;
     const int ny = (p.Cout + bn - 1) / bn;
-    int gx = 256 / ny;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = falnet_persistent_gx(256, ny, ntiles, max_wgs);
     const dim3 grid((unsigned)gx, (unsigned)ny);
+    FALNET_COUNT_ONLY(count, gx * ny);
 #define SF_L(T) do { if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_s2f_dma_kernel<T, 128>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles); \
                      else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_s2f_dma_kernel<T, 64>), grid, dim3(512), 0, st, p, tiles_x, tiles_y, ntiles); } while (0)
     FALNET_DISPATCH_16(p.dtype, SF_L);

@@ -384,7 +384,7 @@ bool falnet_conv_wave64p_applicable(const falnet_conv_t& p) {
     return true;
 }
 
-int falnet_conv_wave64p_launch(const falnet_conv_t& p, int flip, hipStream_t st) {
+int falnet_conv_wave64p_launch(const falnet_conv_t& p, int flip, hipStream_t st, int* count) {
     const int nstrips = (p.OW + 15) / 16;
     const int RB = p.OH >= 32 ? 32 : p.OH;
     const int nyb = (p.OH + RB - 1) / RB;
@@ -392,6 +392,7 @@ int falnet_conv_wave64p_launch(const falnet_conv_t& p, int flip, hipStream_t st)
     int wgs = (int)((units + 8 * RB - 1) / (8 * RB));
     if (wgs > 256) wgs = 256;
     if (wgs < 1) wgs = 1;
+    FALNET_COUNT_ONLY(count, wgs);
 #define CP_L(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_wave64p_kernel<T>), dim3((unsigned)wgs), dim3(CW_THREADS), 0, st, p, nstrips, flip, RB, nyb)
     FALNET_DISPATCH_16(p.dtype, CP_L);
 #undef CP_L
@@ -409,7 +410,7 @@ bool falnet_conv_wave32_applicable(const falnet_conv_t& p) {
     return true;
 }
 
-int falnet_conv_wave32_launch(const falnet_conv_t& p, int flip, hipStream_t st) {
+int falnet_conv_wave32_launch(const falnet_conv_t& p, int flip, hipStream_t st, int* count) {
     const int nstrips = (p.OW + 31) / 32;
     const int RB = p.OH >= 16 ? 16 : p.OH;  // rows per block = one wave's range when the map is large enough
     const int nyb = (p.OH + RB - 1) / RB;
@@ -417,6 +418,7 @@ int falnet_conv_wave32_launch(const falnet_conv_t& p, int flip, hipStream_t st) 
     int wgs = (int)((units + 8 * RB - 1) / (8 * RB));  // one block-strip column per wave (two of a range's steps are halo rows)
     if (wgs > 256) wgs = 256;
     if (wgs < 1) wgs = 1;
+    FALNET_COUNT_ONLY(count, wgs);
 #define CW_L(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_wave32_kernel<T>), dim3((unsigned)wgs), dim3(CW_THREADS), 0, st, p, nstrips, flip, RB, nyb)
     FALNET_DISPATCH_16(p.dtype, CW_L);
 #undef CW_L

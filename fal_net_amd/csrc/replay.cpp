@@ -82,6 +82,7 @@ const Op g_ops[] = {
     FALNET_OP(falnet_resize_planar), FALNET_OP(falnet_disp_prologue), FALNET_OP(falnet_resample_u8), FALNET_OP(falnet_augment_normalize),
     FALNET_OP(falnet_fill_f32), FALNET_OP(falnet_copy_bytes), FALNET_OP(falnet_spin), FALNET_OP(falnet_adam_pack_batched_wd),
     FALNET_OP(falnet_adam_ranges_wd), FALNET_OP(falnet_adam_step_wd), FALNET_OP(falnet_augment_batch), FALNET_OP(falnet_maxpool2_bwd_codes),
+    FALNET_OP(falnet_conv2d_wgs), FALNET_OP(falnet_conv2d_multi_wgs),
 };
 constexpr int g_nops = (int)(sizeof(g_ops) / sizeof(g_ops[0]));
 

@@ -43,13 +43,17 @@ def _release_plan(plan, gen):
 class _VggPlan:
     """Static launch plan of VGG19 features[0:19] forward + data-gradient for one (B,H,W,dtype)."""
 
-    def __init__(self, owner, B, H, W, dtype, device, need_grad=True, pool_codes=None, pool_variant=None):
+    def __init__(self, owner, B, H, W, dtype, device, need_grad=True, pool_codes=None, pool_variant=None, max_wgs=None):
         """need_grad=False (label features, Train_Stage1_K.py:241-244 under no_grad): the convs in front of a pool keep only
         their pooled map (fused pool, no full-resolution store) and no backward launches are built.
         pool_codes (need_grad=True; None = the FALNET_POOL_CODES experiment switch, on by default): the conv in front of a pool keeps its pooled map
         and one 4-bit argmax code per pooled element (falnet_conv_t::pool_code) instead of the full-resolution map, whose only reader was the pool's
         backward; per slice, where the kernel does not apply (f32, maps under 16 x 32) the full-resolution form is built as before.
-        pool_variant: forced falnet_conv2d variant of those convs in the full-resolution form (tests: the same kernel on both sides)."""
+        pool_variant: forced falnet_conv2d variant of those convs in the full-resolution form (tests: the same kernel on both sides).
+        max_wgs (need_grad=False only): workgroup budget of the pass's persistent convs (ops.conv_call) -- the label pass that runs beside the
+        network's deep levels leaves them CUs; a launch with fewer workgroups than the budget is unchanged, so is the first-layer kernel."""
+        assert not (max_wgs and need_grad), "a workgroup budget is for the gradient-free label pass"
+        self.max_wgs = max_wgs or 0
         self.B, self.H, self.W, self.dtype, self.device = B, H, W, dtype, device
         self.busy, self.need_grad, self.gen = False, need_grad, 0
         if pool_codes is None:
@@ -57,7 +61,7 @@ class _VggPlan:
         self.pool_maps, self.pool_codes = [], []  # per slice: the full-resolution map in front of the pool / its argmax codes (one of them is None)
         code = L.dtype_code(dtype)
         self.fwd, self.bwd = [], []
-        _conv = lambda *a, **kw: ops.conv_call(*a, ws_owner=("vgg", id(self)), **kw)  # own split-K scratch per plan instance
+        _conv = lambda *a, **kw: ops.conv_call(*a, ws_owner=("vgg", id(self)), max_wgs=self.max_wgs, **kw)  # own split-K scratch per plan instance
         pcs = owner._packed
         x_in = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
         x0 = x_in  # the first conv reads the planar f32 image directly (falnet_conv3x3_c3): no layout conversion
@@ -106,6 +110,12 @@ class _VggPlan:
             self.pool_codes.append(codes)
             self.outs.append(pooled)
             cur, h, w = pooled, h // 2, w // 2
+        if self.max_wgs and os.environ.get("FALNET_AUTOTUNE_LOG") == "1":
+            import sys
+            for c in self.fwd:
+                if getattr(c, "max_wgs", 0):
+                    full, cut = (L.lib().falnet_conv2d_workgroups(c.ref, m) for m in (0, c.max_wgs))
+                    print(f"[label budget {self.max_wgs}] {c.name}: {full} -> {cut} workgroups", file=sys.stderr)
         self.run_fwd = ops.ReplayList(self.fwd, eager_head=1)  # (the first conv reads the caller's image: set_input per call)
         self.run_bwd = None
         if not need_grad:
@@ -220,13 +230,14 @@ class Vgg19_pc(nn.Module):
                 self._packed[int(i)] = pc
             self._packed_key, self._plans = key, {}
 
-    def _plan(self, B, H, W, dtype, device, hold):
-        pool = self._plans.setdefault((B, H, W, hold), [])  # hold = the call needs a backward (plan busy until it ran)
+    def _plan(self, B, H, W, dtype, device, hold, max_wgs=0):
+        # hold = the call needs a backward (plan busy until it ran); a budgeted label pass has plans of its own
+        pool = self._plans.setdefault((B, H, W, hold, max_wgs) if max_wgs else (B, H, W, hold), [])
         p = next((q for q in pool if not q.busy), None)
         if p is None and hold and len(pool) >= _MAX_HELD_PLANS:
             p = min(pool, key=lambda q: q.gen)  # bounded HBM: recycle the oldest held plan (its backward, if it ever comes, raises)
         if p is None:
-            p = _VggPlan(self, B, H, W, dtype, device, need_grad=hold)
+            p = _VggPlan(self, B, H, W, dtype, device, need_grad=hold, max_wgs=max_wgs)
             pool.append(p)
         self._gen = getattr(self, "_gen", 0) + 1
         p.busy, p.gen = hold, self._gen
@@ -235,9 +246,10 @@ class Vgg19_pc(nn.Module):
                 _GOUT_OF[o.data_ptr()][1] = False  # nobody has written this call's feature gradients yet
         return p
 
-    def forward(self, x, full=False, borrow=False):
+    def forward(self, x, full=False, borrow=False, max_wgs=0):
         """borrow=True (no-grad calls): return views of the plan's output buffers instead of copies -- valid until the next
-        no-grad call with the same input shape (the trainer's per-step label features, Train_Stage1_K.py:241-244)."""
+        no-grad call with the same input shape (the trainer's per-step label features, Train_Stage1_K.py:241-244).
+        max_wgs (no-grad calls; ignored by a gradient-carrying one): workgroup budget of the pass's persistent convs (_VggPlan)."""
         if full:
             raise NotImplementedError("slice4 (relu4_4) is never used on the FAL_net hot path (loss_functions.py:40-42)")
         if not x.is_cuda:
@@ -247,7 +259,7 @@ class Vgg19_pc(nn.Module):
         B, C, H, W = x.shape
         assert C == 3 and H % 8 == 0 and W % 8 == 0, "VGG19 slices need a 3-channel input with H, W divisible by 8"
         need_grad = torch.is_grad_enabled() and x.requires_grad
-        plan = self._plan(B, H, W, dtype, x.device, hold=need_grad)
+        plan = self._plan(B, H, W, dtype, x.device, hold=need_grad, max_wgs=0 if need_grad else int(max_wgs or 0))
         xs = x.float().contiguous() if need_grad else x.detach().float().contiguous()
         if need_grad:
             return _VggFunction.apply(self, plan, xs)

@@ -377,12 +377,17 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
               Cout, out_cstride, out_layout=L.OUT_NHWC, out_step=(1, 1, 0, 0), bias=None, addend=None,
               act=L.ACT_NONE, actout=None, actout_kind=L.ACT_NONE, weight_offset_elems=0, name="conv", flops=0,
               autotune=True, ws_owner=None, pool_out=None, pool_mode=0, pool_actout=None, pool_actout_kind=L.ACT_NONE, weight_up2=None,
-              variant=None, pool_code=None):
+              variant=None, pool_code=None, max_wgs=None):
     """Build one falnet_conv2d launch; returns a zero-argument callable.  `pool_out`: fused 2x2 max pool of the output
     (halo-patch kernels only; `out` may then be None when only the pooled map is needed).  `variant`: this kernel and no other (no autotune;
     ValueError when it does not apply).  `pool_code`: uint8 [B, OH/2, OW/2, out_cstride/2] for the pool's 4-bit argmax codes (falnet_conv_t::pool_code:
-    variant 23 only, so pass variant=23; not part of conv_signature -- a forced variant makes no cache entry)."""
+    variant 23 only, so pass variant=23; not part of conv_signature -- a forced variant makes no cache entry).
+    `max_wgs`: workgroup budget of the launch (falnet_conv2d_wgs: a persistent kernel then runs on at most that many workgroups and leaves the
+    other CUs to launches on other streams; bit-identical results).  Not part of conv_signature either: the choice is the one tuned -- and
+    cached -- at the full grid, and autotune times the full grid."""
     lib = L.lib()
+    if max_wgs is not None and max_wgs < 0:
+        raise ValueError(f"max_wgs = {max_wgs}: a workgroup budget is None / 0 (the full grid) or positive")
     d = L.Conv()
     d.nsrc = len(srcs)
     for i, s in enumerate(srcs):
@@ -439,13 +444,17 @@ def conv_call(dtype, srcs, IH, IW, weight, cin_total, taps, w_taps, w_rows, stri
     if pool_out is not None and lib.falnet_conv2d_kernel_name(ref, C.create_string_buffer(160), 160) != 0:
         raise ValueError("no fused-pool kernel applies to this launch")  # the caller falls back to falnet_maxpool2_fwd
 
-    def launch(_keep=keep):
-        L.check(lib.falnet_conv2d(ref, L.stream_ptr()), name)
+    if max_wgs:
+        def launch(_keep=keep):
+            L.check(lib.falnet_conv2d_wgs(ref, max_wgs, L.stream_ptr()), name)
+    else:
+        def launch(_keep=keep):
+            L.check(lib.falnet_conv2d(ref, L.stream_ptr()), name)
     buf = C.create_string_buffer(160)
     L.check(lib.falnet_conv2d_kernel_name(ref, buf, 160), name)  # (fails exactly when falnet_conv2d would: both ask choose_conv_kernel)
     tag = buf.value.decode()
     call = _timed(tag, flops, 0, launch, f"{name} v{d.variant} k{d.ksplit}")
-    call.desc, call.ref = d, ref
+    call.desc, call.ref, call.max_wgs = d, ref, max_wgs or 0
     return call
 
 
@@ -523,11 +532,12 @@ def gather_bn(w_rows, Cout):
     return 128 if (w_rows % 128 == 0 and Cout > 64) else (64 if (w_rows % 64 == 0 and Cout > 32) else 32)
 
 
-def conv_multi_call(calls, name="conv multi", bn=None, ksplit=1, s2d=False):
+def conv_multi_call(calls, name="conv multi", bn=None, ksplit=1, s2d=False, max_wgs=None):
     """Fuse up to four conv_call launches (built with autotune off: gather kernel) into one falnet_conv2d_multi.
     bn = 32 / 64: narrower workgroups than the default (variants 11 / 12: more workgroups for small layers).
     ksplit > 1: split-K over blockIdx.z with one fused epilogue; the members share the plan's split-K workspace, each with its
-    own region (raises ValueError when it does not fit)."""
+    own region (raises ValueError when it does not fit).
+    max_wgs: workgroup budget (falnet_conv2d_multi_wgs; the persistent s2d kernel takes it, the gather form ignores it)."""
     lib = L.lib()
     if ksplit > 1 and DETERMINISTIC:
         raise ValueError("split-K is not available in deterministic mode")
@@ -549,7 +559,10 @@ def conv_multi_call(calls, name="conv multi", bn=None, ksplit=1, s2d=False):
     bn = bn or gather_bn(arr[0].w_rows, arr[0].Cout)
 
     def launch(_keep=keep):
-        L.check(lib.falnet_conv2d_multi(arr, n, L.stream_ptr()), name)
+        if max_wgs:
+            L.check(lib.falnet_conv2d_multi_wgs(arr, n, max_wgs, L.stream_ptr()), name)
+        else:
+            L.check(lib.falnet_conv2d_multi(arr, n, L.stream_ptr()), name)
     sym = f"_Z22conv3x3_s2d_dma_kernelI{dn}Ev13falnet_conv_tiiiii" if s2d else f"_Z23conv_igemm_multi_kernelI{dn}Li{bn}EEv14falnet_conv4_t"
     return _timed(sym, sum(c.flops for c in calls), 0, launch, name)
 

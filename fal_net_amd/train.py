@@ -349,10 +349,25 @@ def _aux_stream(device):
     return aux_stream(device)
 
 
-def vgg_label_async(label, borrow=True):
+# Workgroup budget of the label pass that starts from the mid-forward hook (falnet_conv2d_wgs; 0 = off).  Its convs are persistent launches of
+# 256 eight-wave workgroups at 256 VGPRs: each holds a whole CU, so the small launches of the network's levels 3-6 on the main stream were only
+# placed when a label kernel retired.  With a budget the label convs leave CUs free for them.  128 of the 256 CUs: the best of the sweep in
+# profiles/label_budget_sweep.txt (2048 tiles of the full-resolution convs = 16 per workgroup, no ragged last round), beside hook level 2.
+LABEL_WGS = int(L.ab("FALNET_LABEL_WGS", "128"))
+
+
+def _label_wgs(label):
+    """Budget of the hooked label pass of this image.  Off above 256 x 512: at 384 x 1280 the label convs are 3.75 times the work beside the same
+    few small launches, and halving their grid cost 1.2 % of the step (profiles/label_budget_vs_parent_same_box.txt)."""
+    return LABEL_WGS if label.shape[-2] * label.shape[-1] <= 256 * 512 else 0
+
+
+def vgg_label_async(label, borrow=True, max_wgs=0):
     """VGG features of a label image on an auxiliary HIP stream: independent of the network forward, so it runs
     concurrently with it and fills the CUs the small backbone layers leave idle.  Returns join() -> features.
-    `borrow`: the features alias the label plan's buffers (valid until the next label pass of that shape)."""
+    `borrow`: the features alias the label plan's buffers (valid until the next label pass of that shape).
+    `max_wgs`: workgroup budget of the pass's persistent convs (LABEL_WGS for the pass started from the mid-forward hook; every other
+    caller, and the instrumented serial pass, runs the full grid)."""
     if ops.TIMER is not None:  # instrumented pass (bench.py roofline): serial launches so per-kernel times are uncontended
         feats_serial = vgg(label, borrow=borrow)
         return lambda: feats_serial
@@ -360,7 +375,7 @@ def vgg_label_async(label, borrow=True):
     aux = _aux_stream(label.device)
     aux.wait_stream(main)
     with torch.cuda.stream(aux), L.on_stream(aux):  # (torch stream for the allocator / record_stream, pinned pointer for the launches)
-        feats = vgg(label, borrow=borrow)  # consumed by this step's perceptual loss only
+        feats = vgg(label, borrow=borrow, max_wgs=max_wgs)  # consumed by this step's perceptual loss only
 
     def join():
         main.wait_stream(aux)
@@ -433,7 +448,7 @@ def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_ar
     joins = []
     if a_p > 0:
         if L.ab("FALNET_LABEL_VGG_MID", "1") == "1" and ops.TIMER is None:
-            model._mid_forward_hook = lambda: joins.append(vgg_label_async(right))
+            model._mid_forward_hook = lambda: joins.append(vgg_label_async(right, max_wgs=_label_wgs(right)))
         else:
             joins.append(vgg_label_async(right))
     lf = left.detach()
@@ -525,7 +540,7 @@ def stage1_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 / 512,
     joins = []
     if a_p > 0:
         if L.ab("FALNET_LABEL_VGG_MID", "1") == "1" and ops.TIMER is None:
-            model._mid_forward_hook = lambda: joins.append(vgg_label_async(right))
+            model._mid_forward_hook = lambda: joins.append(vgg_label_async(right, max_wgs=_label_wgs(right)))
         else:
             joins.append(vgg_label_async(right))
     rpan, ldisp = model(left, min_disp, max_disp, ret_disp=True, ret_pan=True, ret_subocc=False)  # :238

@@ -170,7 +170,19 @@ typedef struct {
                                   values as rounded to `dtype`), 0 when the pooled value is not > 0 -- all that falnet_maxpool2_bwd_codes needs, so
                                   `out` may stay NULL on a gradient-carrying pass.  Private to these two entry points */
 } falnet_conv_t;
-int falnet_conv2d(const falnet_conv_t* p, void* stream);
+int falnet_conv2d(const falnet_conv_t* p, void* stream); /* = falnet_conv2d_wgs(p, 0, stream) */
+/* The same launch under a WORKGROUP BUDGET: max_workgroups = 0 is falnet_conv2d's grid; > 0 caps the total number of workgroups of a
+ * PERSISTENT launch, so that it leaves compute units to launches on other streams (a full-grid persistent workgroup holds a whole CU's
+ * registers: nothing co-resides).  With ny output-channel blocks the grid is gx x ny, gx = max(1, min(max_workgroups, full) / ny), clamped
+ * to the number of tiles as before; full = 256 (512 for variant 21, two workgroups per CU).  Every persistent kernel strides its tile loop
+ * by the grid width, so which workgroup computes a tile does not enter the arithmetic: the result is bit-identical for every budget.
+ * Budgeted: the LDS-DMA variants 13 / 17 / 20, 21 / 22, 23 / 24 / 25, 15, 18, 26 and the weight-stationary variants 10 / 16.  A family that
+ * is not persistent, or sums through f32 atomics or split-K (gather 1 / 11 / 12, halo-patch 2-9, 19, wave-streaming 27 / 29), accepts the
+ * argument and ignores it; falnet_conv3x3_c3 is not a persistent launcher and takes none.  < 0: refused (-1) before anything is launched. */
+int falnet_conv2d_wgs(const falnet_conv_t* p, int max_workgroups, void* stream);
+/* Workgroups falnet_conv2d_wgs(p, max_workgroups, .) would launch (all grid dimensions multiplied; the split-K epilogue launch of the gather
+ * kernel not counted): the same checks, kernel choice and grid arithmetic, no device call.  Negative: the error code, falnet_last_error() set. */
+int falnet_conv2d_workgroups(const falnet_conv_t* p, int max_workgroups);
 /* First layer: 3x3 / stride 1 / pad 1 convolution of a 3-channel planar f32 image (FAL_netB.py:99 conv0, VGG19 features[0];
  * loss_functions.py:21) with the f32 OIHW weights as they are -> NHWC `dtype` [B][H][W][Cout], Cout in {32, 64}, bias + act fused. */
 int falnet_conv3x3_c3(const float* x_nchw, const float* w_oihw, const float* bias, void* out, int B, int H, int W, int Cout,
@@ -181,7 +193,9 @@ int falnet_conv3x3_c3(const float* x_nchw, const float* w_oihw, const float* bia
 /* variant 14 in descs[0]: the members must be the four output-parity classes (0,0) (0,1) (1,0) (1,1) of ONE 3x3 / stride-2 / pad-1
  * data gradient in bf16 / f16 (same gout source, packed weight, output tensor; taps as fal_net_amd/ops.py:dgrad_taps_s2); they then
  * run as one LDS-DMA halo kernel (csrc/conv_dma.hip: conv3x3_s2d_dma_kernel) instead of four gather GEMMs. */
-int falnet_conv2d_multi(const falnet_conv_t* descs, int n, void* stream);
+int falnet_conv2d_multi(const falnet_conv_t* descs, int n, void* stream); /* = falnet_conv2d_multi_wgs(descs, n, 0, stream) */
+/* ... under a workgroup budget (falnet_conv2d_wgs): the persistent variant-14 kernel takes it, the gather form ignores it; < 0 is refused */
+int falnet_conv2d_multi_wgs(const falnet_conv_t* descs, int n, int max_workgroups, void* stream);
 /* symbol (as rocprofv3 reports it) of the kernel falnet_conv2d launches for this descriptor */
 int falnet_conv2d_kernel_name(const falnet_conv_t* p, char* buf, int len);
 
