@@ -1077,7 +1077,7 @@ static WgradKernel choose_wgrad_kernel(const falnet_wgrad_t& p) {
         return WGK_WAVE;
     }
     if (p.variant == 7) {
-        if (!falnet_wgrad_rows_applicable(p)) { falnet_set_error("wgrad: variant 7 needs a 16-bit dense 3x3 stride-1 launch with sources at the launch size or half of it (up2: ONE source at the launch size, nsplit a multiple of 4)"); return WGK_BAD; }
+        if (!falnet_wgrad_rows_applicable(p)) { falnet_set_error("wgrad: variant 7 needs a 16-bit dense 3x3 stride-1 launch with sources at the launch size or half of it (up2: ONE source at the launch size; up2 = 1: nsplit a multiple of 4)"); return WGK_BAD; }
         return WGK_ROWS;
     }
     // dense 3x3 stride-1 -> halo-patch kernel (one slab per workgroup; nsplit = pixel-range splits)

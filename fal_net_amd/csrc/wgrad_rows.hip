@@ -1023,6 +1023,270 @@ __global__ __launch_bounds__(WR8_THREADS, 2) void wgrad3x3_rows16_kernel(const f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// wgrad3x3_up2q_kernel (falnet_wgrad_t::up2 = 2): the `deconv` weight gradient on the low-resolution grid with ALL FOUR parity classes in one step.
+//
+// The UP2 form above removes the tap products the result does not need but none of the row steps: its four classes each walk the whole low-resolution
+// grid and fetch every input row again, and a step of this kernel family costs the same whether its waves issue 36 MFMAs or 16.  Here a split is a
+// plain range of (sample, strip, LOW-resolution row) units, and a step carries two low-resolution rows: the eight class rows g[2 y + py][2 x + px]
+// (8 x 4 KB, gathered with pixel stride 2 gC by the LDS-DMA as above) and two input rows (2 x 5 KB) -- a quarter of the high-resolution form's steps,
+// the input fetched once.  Class row (r, py) meets input rows r - 1 + py and r + py (ky' = py, py + 1), so the INPUT fragments (three column offsets
+// per row) live in the rolling register window -- two rows back -- and the class-row fragments are read when their MFMAs are issued: step t loads
+// input rows 2t - 1, 2t and class rows 2t - 2, 2t - 1 of its item (the first step of an item only primes the window), 16 class fragments x (2 ky' x
+// 2 kx') = 64 MFMAs per wave.  The 16 products S[py, px][ky', kx'] keep their own accumulators (16 x 2 gout tiles x 4 registers); the epilogue sums
+// the four that feed each of the nine taps in registers, in one fixed order, and writes every slab element once.  Wave roles, LDS row image,
+// swizzles, zero page and counted vmcnt as in wgrad3x3_rows16_kernel; ring of D + 1 slots, one barrier per step, in front of which every wave has
+// waited for its own fragment reads of the step before (lgkmcnt(0)): the slot the step refills was last read then.
+#define WQ_SLOT (8 * WR_GROW + 2 * WR_XROW)  // 42 KiB: class rows (rsel, py, px), input rows j0, j1
+
+template <typename T, int D>
+__global__ __launch_bounds__(WR8_THREADS, 2) void wgrad3x3_up2q_kernel(const falnet_wgrad_t p, int w_rows, int ntci, int ntiles, int nstrips) {
+    constexpr int NS = D + 1;
+    static_assert(D >= 1 && D <= 2 && NS * WQ_SLOT <= 160 * 1024, "prefetch distance / ring must fit in LDS");
+    __shared__ __attribute__((aligned(1024))) char lds[NS * WQ_SLOT];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned lds_base = (unsigned)(unsigned long)(wr_lptr_t)lds;
+    const int nsplit = p.nsplit;
+    int tile, split;
+    {
+        const int wg = blockIdx.x;
+        if ((nsplit & 7) == 0) {  // the channel tiles of one pixel range share an XCD (blocks b and b + 8 do)
+            const int idx = wg >> 3;
+            split = (idx / ntiles) * 8 + (wg & 7);
+            tile = idx % ntiles;
+        } else {
+            tile = wg % ntiles;
+            split = wg / ntiles;
+        }
+    }
+    const int ci0 = (tile % ntci) * 64, co0 = (tile / ntci) * 64;
+    const int c_t = wave & 1, a_q = wave >> 1;   // MFMA role: 32 gout channels (two 16-channel tiles), 16 input channels
+    const int rsel = wave >> 2, pw = wave & 3;   // DMA role: row of the step's pair, 8-pixel piece
+    const int H = p.TH, TW = p.TW, gC = p.gC, IH = p.IH;  // the LOW-resolution grid
+    const int R = p.B * nstrips * H;
+    const int u0 = (int)((int64_t)R * split / nsplit), u1 = (int)((int64_t)R * (split + 1) / nsplit);
+
+    // ---- per-lane DMA geometry (as wgrad3x3_rows16_kernel) ----
+    const int pl = lane >> 3, cpos = lane & 7;
+    const int gch = cpos ^ ((((pl >> 1) & 1) << 2) | ((pw & 1) << 1));
+    const char* const zero_page = reinterpret_cast<const char*>(g_wr_zero);
+    const bool g_chok = co0 + 8 * gch < gC;
+    const int ch = ci0 + 8 * gch;
+    const bool x_chok = ch < p.cin_total;
+    const falnet_src_t& S = p.src[0];
+    const int64_t l_sy = S.sy, l_sx = S.sx, l_sb = S.sb;
+    const T* const l_ptr = reinterpret_cast<const T*>(S.ptr) + ch;
+
+    auto load_item = [&](Wr8Item& c, int u) {
+        c.u = u;
+        const int bs = u / H;
+        c.y0 = u - bs * H;
+        c.n = min((bs + 1) * H, u1) - u;
+        c.T = (c.n + 3) >> 1;
+        c.b = bs / nstrips;
+        c.x0 = (bs - c.b * nstrips) * WR_TW;
+        c.t = 0;
+    };
+    int nst = 0;
+    for (int u = u0; u < u1;) {
+        const int e = min((u / H + 1) * H, u1);
+        nst += (e - u + 3) >> 1;
+        u = e;
+    }
+    // running per-lane source pointers of this wave's pieces: class rows y0 - 2 + rsel + 2t (class (py, px) at byte offset py g_py + px g_px; the
+    // pointer of a row in front of the item is never dereferenced), input rows y0 - 1 + rsel + 2t; lanes outside the map sit on the zero page
+    const char* gptr = zero_page;
+    const char* xptr = zero_page;
+    const char* x4ptr = zero_page;
+    unsigned g_inc = 0, g_py = 0, g_px = 0, x_inc = 0, x4_inc = 0;
+    auto item_pointers = [&](const Wr8Item& c) {
+        const int gx = c.x0 + 8 * pw + pl;
+        const bool g_ok = g_chok && gx < TW;
+        gptr = g_ok ? reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.gout) +
+                                                    ((((int64_t)c.b * 2 * H + 2 * (c.y0 - 2 + rsel)) * (2 * TW)) + 2 * gx) * gC + co0 + 8 * gch) : zero_page;
+        g_inc = g_ok ? (unsigned)(8 * TW * gC * (int)sizeof(T)) : 0u;
+        g_py = g_ok ? (unsigned)(2 * TW * gC * (int)sizeof(T)) : 0u;
+        g_px = g_ok ? (unsigned)(gC * (int)sizeof(T)) : 0u;
+        const int i = c.y0 - 1 + rsel;
+        const int64_t rowoff = (int64_t)c.b * l_sb + (int64_t)i * l_sy;
+        const unsigned xi = (unsigned)(2 * l_sy * (int)sizeof(T));
+        const int xa = c.x0 - 1 + 8 * pw + pl;
+        const bool x_ok = x_chok && xa >= 0 && xa < p.IW;
+        xptr = x_ok ? reinterpret_cast<const char*>(l_ptr + rowoff + (int64_t)xa * l_sx) : zero_page;
+        x_inc = x_ok ? xi : 0u;
+        const int xb = c.x0 - 1 + 32 + pl;  // (issued by the pw == 0 waves only)
+        const bool x4_ok = x_chok && pl < 2 && xb < p.IW;
+        x4ptr = x4_ok ? reinterpret_cast<const char*>(l_ptr + rowoff + (int64_t)xb * l_sx) : zero_page;
+        x4_inc = x4_ok ? xi : 0u;
+    };
+    auto issue_piece = [&](const Wr8Item& c, int slot, int k) {  // k = 0..3 class row (py, px) = (k >> 1, k & 1), 4 input row, 5 its two halo pixels
+        const unsigned base = lds_base + slot * WQ_SLOT;
+        if (k < 4) {
+            const bool gv = (unsigned)(2 * c.t - 2 + rsel) < (unsigned)c.n;  // class row inside the item
+            wr_glds16(gv ? gptr + (k >> 1) * g_py + (k & 1) * g_px : zero_page, base + (rsel * 4 + k) * WR_GROW + pw * 1024);
+            if (k == 3) gptr += g_inc;
+            return;
+        }
+        const int i = c.y0 - 1 + 2 * c.t + rsel;
+        const bool xv = i >= 0 && i < IH;  // input row inside the image
+        if (k == 4) {
+            wr_glds16(xv ? xptr : zero_page, base + 8 * WR_GROW + rsel * WR_XROW + pw * 1024);
+            xptr += x_inc;
+        } else if (pw == 0) {
+            wr_glds16(xv ? x4ptr : zero_page, base + 8 * WR_GROW + rsel * WR_XROW + 4 * 1024);
+            x4ptr += x4_inc;
+        }
+    };
+
+    // ---- fragment read geometry (as wgrad3x3_rows16_kernel) ----
+    const int i16 = lane & 15, g16 = lane >> 4;
+    const int q = i16 >> 2, pc = i16 & 3;
+    auto frag_off = [&](int cb16, int pshift, int second_read) {
+        const int px = 8 * g16 + q + pshift + 4 * second_read;
+        const int chunk = 2 * cb16 + (pc >> 1);
+        const int sw = (((px >> 1) & 1) << 2) | (((px >> 3) & 1) << 1);
+        return px * 128 + ((chunk ^ sw) * 16) + (pc & 1) * 8;
+    };
+    int offA[2][2], offB[3][2];  // [gout tile cc][read], [column offset][read]
+#pragma unroll
+    for (int rd = 0; rd < 2; ++rd) {
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) offA[cc][rd] = frag_off(2 * c_t + cc, 0, rd);
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) offB[dx][rd] = 8 * WR_GROW + frag_off(a_q, dx, rd);
+    }
+    auto frag = [&](const char* base, const int (&off)[2]) -> s16x8 {
+        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wr_lds_v4)(base + off[0]));
+        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wr_lds_v4)(base + off[1]));
+        return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+
+    f32x4_t acc[2][2][2][2][2];  // [py][px][ky' - py][kx' - px][gout tile]
+#pragma unroll
+    for (int e = 0; e < 32; ++e) (&acc[0][0][0][0][0])[e] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    s16x8 xw[4][3];  // input fragments of rows 2t - 3, 2t - 2 (the window) and 2t - 1, 2t (this step's), per column offset
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xw[r][dx][j] = 0;
+    const bool a_live = ci0 + 16 * a_q < p.cin_total && co0 + 32 * c_t < gC;
+    const bool do_bias = p.bias_grad != nullptr && (tile % ntci) == 0 && a_q == 0;
+    float bsum[2] = {0.f, 0.f};
+
+    Wr8Item ci_, cc_;
+    if (nst > 0) {
+        load_item(ci_, u0);
+        cc_ = ci_;
+        item_pointers(ci_);
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (d < nst) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) issue_piece(ci_, d, k);
+                if (d + 1 < nst && ++ci_.t == ci_.T) {
+                    load_item(ci_, ci_.u + ci_.n);
+                    item_pointers(ci_);
+                }
+            }
+        }
+    }
+    int slot = 0, islot = D;
+    for (int g = 0; g < nst; ++g) {
+        const bool do_issue = g + D < nst;
+        // this wave's pieces of step g have landed once at most one younger step's worth (6 / 5 pieces) is outstanding
+        if (D >= 2 && g + 1 < nst) {
+            if (pw == 0) wr_vmcnt<6>();
+            else wr_vmcnt<5>();
+        } else {
+            wr_vmcnt<0>();
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own fragment reads of step g - 1 are done: its slot is refilled below
+        __builtin_amdgcn_s_barrier();
+        const char* sb = lds + slot * WQ_SLOT;
+        const int t2 = 2 * cc_.t, n = cc_.n;
+        const bool v_row[2] = {(unsigned)(t2 - 2) < (unsigned)n, (unsigned)(t2 - 1) < (unsigned)n};  // class rows 2t - 2, 2t - 1 inside the item
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            xw[2][dx] = frag(sb, offB[dx]);
+            xw[3][dx] = frag(sb + WR_XROW, offB[dx]);
+        }
+        // DMA pieces of step g + D go between the MFMA groups (a piece holds its wave in issue; the matrix pipe works on the group before it)
+#pragma unroll
+        for (int grp = 0; grp < 8; ++grp) {
+            const int row = grp >> 2, py = (grp >> 1) & 1, px = grp & 1;
+            if (a_live && v_row[row]) {  // class row r = 2t - 2 + row: input rows r - 1, r, r + 1 are xw[row], xw[row + 1], xw[row + 2]
+#pragma unroll
+                for (int cc = 0; cc < 2; ++cc) {
+                    const s16x8 a = frag(sb + (row * 4 + py * 2 + px) * WR_GROW, offA[cc]);
+                    if (do_bias) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bsum[cc] += Mma16<T>::f32(a[j]);
+                    }
+#pragma unroll
+                    for (int kyi = 0; kyi < 2; ++kyi)
+#pragma unroll
+                        for (int kxi = 0; kxi < 2; ++kxi)
+                            acc[py][px][kyi][kxi][cc] = H16<T>::mma16(a, xw[row + py + kyi][px + kxi], acc[py][px][kyi][kxi][cc]);
+                }
+            }
+            if (grp < 6 && do_issue) {
+                __builtin_amdgcn_sched_barrier(0);
+                issue_piece(ci_, islot, grp);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (do_issue && g + D + 1 < nst && ++ci_.t == ci_.T) {
+            load_item(ci_, ci_.u + ci_.n);
+            item_pointers(ci_);
+        }
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            xw[0][dx] = xw[2][dx];
+            xw[1][dx] = xw[3][dx];
+        }
+        if (g + 1 < nst && ++cc_.t == cc_.T) load_item(cc_, cc_.u + cc_.n);
+        slot = slot + 1 == NS ? 0 : slot + 1;
+        islot = islot + 1 == NS ? 0 : islot + 1;
+    }
+
+    if (do_bias) {  // lane (i16, g16) summed pixels 8 g16 .. 8 g16 + 7 of every class row for channel co0 + 32 c_t + 16 cc + i16
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            float b = bsum[cc];
+            b += __shfl_xor(b, 16, 64);
+            b += __shfl_xor(b, 32, 64);
+            const int co = co0 + 32 * c_t + 16 * cc + i16;
+            if (g16 == 0 && co < p.cout) atomicAdd(p.bias_grad + co, b);
+        }
+    }
+    // ---- slab: tap (ky, kx) of the 3x3 gradient = sum over the classes (py, px) of S[py, px][ky', kx'], ky' = ((py + ky - 1) >> 1) + 1 ----
+    const int ci = ci0 + 16 * a_q + i16;
+    if (ci < p.cin_total) {
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                float* dst = p.partial + (((int64_t)split * 9 + ky * 3 + kx) * w_rows) * p.cin_total;
+#pragma unroll
+                for (int cc = 0; cc < 2; ++cc) {
+                    f32x4_t v = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int py = 0; py < 2; ++py)
+#pragma unroll
+                        for (int px = 0; px < 2; ++px) v += acc[py][px][((py + ky - 1) >> 1) + 1 - py][((px + kx - 1) >> 1) + 1 - px][cc];
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) {
+                        const int co = co0 + 32 * c_t + 16 * cc + 4 * g16 + f;
+                        if (co < w_rows) dst[(int64_t)co * p.cin_total + ci] = v[f];
+                    }
+                }
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Stride-2 form of the eight-wave kernel (encoder convs conv2..conv4, FAL_netB.py:103-107: 3x3, stride 2, pad 1):
 //   dW[co][ky][kx][ci] = sum over output pixels (i, j) of gout[i][j][co] * in[2 i + ky - 1][2 j + kx - 1][ci]
 // Same roles (16-pixel half x 32-channel sub-tiles, one workgroup per CU, accumulators summed through LDS), same ring of row slots
@@ -1388,7 +1652,9 @@ bool falnet_wgrad_rows_applicable(const falnet_wgrad_t& p) {
     }
     if (ctot != p.cin_total) return false;
     if ((int64_t)p.B * ((p.TW + WR_TW - 1) / WR_TW) * p.TH >= (1ll << 30)) return false;
-    // up2: gout is the upstream gradient at [B][2 TH][2 TW][gC], ONE source at the launch size, splits in whole groups of the four parity classes
+    // up2 = 2 (all four parity classes per step): gout is the upstream gradient at [B][2 TH][2 TW][gC], ONE source at the launch size, any split count
+    if (p.up2 == 2) return p.nsrc == 1 && p.src[0].H == p.IH && p.src[0].W == p.IW && p.nsplit >= 1 && (int64_t)8 * p.TW * p.gC * 2 < (1ll << 31);
+    // up2 = 1: the same operands, splits in whole groups of the four parity classes
     if (p.up2 && (p.nsrc != 1 || p.src[0].H != p.IH || p.src[0].W != p.IW || p.nsplit < 4 || (p.nsplit & 3) || (int64_t)8 * p.TW * p.gC * 2 >= (1ll << 31))) return false;
     return true;
 }
@@ -1444,6 +1710,11 @@ int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, hipStream_t st) {
     }
 #endif
     // the product kernel: v_mfma_f32_16x16x32 (round 5: -7 % on the launches alone, -0.9 % on the step: profiles/r05_ab_rows16.txt)
+    if (p.up2 == 2) {  // a `deconv` layer's weight gradient on the low-resolution grid, four parity classes per step: splits = pixel ranges
+        if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_up2q_kernel<f16_t, 2>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_up2q_kernel<bf16_t, 2>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
+        FALNET_RETURN_LAUNCH();
+    }
     if (p.up2) {  // a `deconv` layer's weight gradient on the low-resolution grid: splits = (pixel range, parity class)
         if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<f16_t, 4, 2, true>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<bf16_t, 4, 2, true>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);

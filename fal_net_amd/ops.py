@@ -27,8 +27,12 @@ AUTOTUNE = os.environ.get("FALNET_AUTOTUNE", "1") != "0"
 # timing launches, whose winner can differ from run to run --, no split-K (f32 atomics), one writer per element in the slab reduce,
 # bias gradients through the two-pass ordered form; the library side is falnet_set_deterministic (fal_net_amd/_lib.py sets it).
 DETERMINISTIC = L.DETERMINISTIC
-UP2W = L.ab("FALNET_UP2W", "0") == "1"  # deconv weight gradients on the low-resolution grid (falnet_wgrad_t::up2): correct and tested, NOT faster -- the
-# row-streaming kernel's step is bound by its DMA / barrier cadence, not by its MFMAs (profiles/r05_ab_up2w.txt) -- so off by default
+UP2W = L.ab("FALNET_UP2W", "0") == "1"  # deconv weight gradients on the low-resolution grid, ONE parity class per split (falnet_wgrad_t::up2 = 1): correct and
+# tested, NOT faster -- its four classes each walk the whole grid, so it saves MFMAs but no row steps, and the row-streaming kernel's step is bound by its
+# DMA / barrier cadence, not by its MFMAs (profiles/r05_ab_up2w.txt) -- so off by default.  Layers listed in UP2Q take the four-class form instead.
+UP2Q = frozenset(k for k in L.ab("FALNET_UP2Q", "deconv1,deconv2,deconv3,deconv4").split(",") if k)  # deconv layers whose weight gradient runs with all four parity
+# classes per low-resolution row step (falnet_wgrad_t::up2 = 2, wgrad3x3_up2q_kernel): a quarter of the high-resolution form's steps, the input fetched
+# once.  Per layer, by the isolated launches of profiles/up2w_quad_isolated.txt: a layer where the form is not faster stays off this list.
 UP2D = L.ab("FALNET_UP2D", "1") == "1"  # deconv data gradients on the low-resolution grid (falnet_conv2d variant 26) among the plan's candidates
 
 
@@ -642,10 +646,11 @@ def _autotune_conv(lib, d, ref, M, w_rows, Cout, reps=3):
     return best
 
 
-def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_pad, max_slabs, target_wgs=1536, up2=False):
+def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_pad, max_slabs, target_wgs=1536, up2=0):
     """(variant, nsplit, kernel symbol) of one weight-gradient launch -- the host-side mirror of wgrad.hip's kernel choice
     (falnet_wgrad re-checks the variant and fails loudly; whether the bias gradient is fused is ASKED from the library,
-    falnet_wgrad_fuses_bias, never re-derived here)."""
+    falnet_wgrad_fuses_bias, never re-derived here).  up2: falnet_wgrad_t::up2 (0, 1 = one parity class per split, 2 = all four per step)."""
+    up2 = int(up2)
     M = B * TH * TW
     h16 = dtype in (torch.bfloat16, torch.float16)
     tn = TYPE_SYM[dtype]
@@ -683,16 +688,18 @@ def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_p
         variant, sym = 9, f"_Z22wgrad3x3_wave32_kernelI{tn}Li{cout_pad // 32}ELb0EEv14falnet_wgrad_ti"
     elif _wgrad_rows(dtype, dense, srcs, IH, IW, TW, cin_pad, cout_pad):
         tiles = ((cin_pad + 63) // 64) * ((cout_pad + 63) // 64)
-        units = B * ((TW + 31) // 32) * TH * (4 if up2 else 1)  # up2: every parity class walks the whole low-resolution grid
+        units = B * ((TW + 31) // 32) * TH * (4 if up2 == 1 else 1)  # up2 = 1: every parity class walks the whole low-resolution grid
         nsplit = max(1, min(_WGRAD_ROWS_WGS // tiles, units // _WGRAD_ROWS_MIN_ROWS))
         if nsplit >= 8:
             nsplit -= nsplit % 8  # multiples of 8: the channel tiles of one pixel range then share an XCD
-        if up2:
+        if up2 == 1:
             nsplit = max(4, nsplit - nsplit % 4)  # whole groups of the four parity classes
             max_slabs -= max_slabs % 4
             if max_slabs < 4:
                 raise ValueError("up2 weight gradient: the slab budget holds fewer than four slabs")
-        variant, sym = 7, f"_Z22wgrad3x3_rows16_kernelI{tn}Li4ELi2ELb{int(up2)}EEv14falnet_wgrad_tiiii"
+        variant, sym = 7, f"_Z22wgrad3x3_rows16_kernelI{tn}Li4ELi2ELb{int(up2 == 1)}EEv14falnet_wgrad_tiiii"
+        if up2 == 2:  # four parity classes per step (wgrad3x3_up2q_kernel): splits are plain ranges of low-resolution rows, any count
+            sym = f"_Z20wgrad3x3_up2q_kernelI{tn}Li2EEv14falnet_wgrad_tiiii"
     elif up2:
         raise ValueError("up2 weight gradient: the row-streaming kernel does not apply")
     elif dense:
@@ -733,7 +740,7 @@ def _fuse_bias(lib, d, grad_b):
 
 
 def wgrad_calls(dtype, srcs, IH, IW, gout, taps, stride_in, B, TH, TW, pc, grad_w, grad_b, ws, target_wgs=1536,
-                name="wgrad", flops=0, up2=False):
+                name="wgrad", flops=0, up2=0):
     """Weight (+bias) gradient of one conv: split-K partial slabs in `ws`, then a reduce into the
     OIHW f32 views `grad_w` / `grad_b`.  Returns a callable taking (accumulate).  up2: as WgradBatch.add."""
     lib = L.lib()
@@ -863,8 +870,8 @@ class WgradBatch:
         self.ws = None
         self.accumulate = 1  # set per backward by the plan: 0 = the step's gradient buffer was zeroed, single-writer entries may overwrite
 
-    def add(self, srcs, IH, IW, gout, taps, stride_in, B, TH, TW, pc, grad_w, grad_b, name="wgrad", flops=0, bucket=0, up2=False):
-        """up2: the weight gradient of a `deconv` layer on the LOW-resolution grid (falnet_wgrad_t::up2): `gout` at [B][2 TH][2 TW][gC], the one
+    def add(self, srcs, IH, IW, gout, taps, stride_in, B, TH, TW, pc, grad_w, grad_b, name="wgrad", flops=0, bucket=0, up2=0):
+        """up2 (1 or 2, the value of falnet_wgrad_t::up2): the weight gradient of a `deconv` layer on the LOW-resolution grid: `gout` at [B][2 TH][2 TW][gC], the one
         source at TH x TW = IH x IW; ValueError when the row-streaming kernel does not apply."""
         lib = L.lib()
         d = L.Wgrad()

@@ -378,7 +378,8 @@ class FalnetPlan:
 
     def _wgrad(self, pc, srcs, IH, IW, gout, name="", on_main=False, up2=False):
         """up2: a `deconv` layer (its one source sits at exactly half of gout's map): the gradient is taken on the LOW-resolution grid where the
-        row-streaming kernel applies (falnet_wgrad_t::up2: 16 instead of 36 tap products per position), else on gout's grid as every other layer's."""
+        row-streaming kernel applies (falnet_wgrad_t::up2: 16 instead of 36 tap products per position; ops.UP2Q lists the layers that take the
+        four-classes-per-step form), else on gout's grid as every other layer's."""
         OH, OW = gout.shape[1], gout.shape[2]
         self._buckets_seen = getattr(self, "_buckets_seen", set()) | {self._bucket}
         gw = self.model._grad_view(pc.weight)
@@ -391,11 +392,12 @@ class FalnetPlan:
                 self._deep_call(call)
             else:
                 self._side_call(call)
-        if up2 and len(srcs) == 1 and pc.stride == 1 and pc.taps == 9 and self.dtype in ops.H16 and ops.UP2W:
+        form = 2 if name in ops.UP2Q else 1 if ops.UP2W else 0  # four parity classes per row step / one class per split / the high-resolution form
+        if up2 and form and len(srcs) == 1 and pc.stride == 1 and pc.taps == 9 and self.dtype in ops.H16:
             try:
                 lh, lw = OH // 2, OW // 2
                 route(self.wbatch.add(srcs, lh, lw, gout, [(dy, dx, 0) for dy, dx, _ in ops.fwd_taps(pc.ksize)], 1, self.B, lh, lw, pc, gw, gb,
-                                      name="wgrad(low-res) " + name, flops=2 * self.B * OH * OW * pc.cout * pc.cin * pc.taps, bucket=self._bucket, up2=True))
+                                      name="wgrad(low-res) " + name, flops=2 * self.B * OH * OW * pc.cout * pc.cin * pc.taps, bucket=self._bucket, up2=form))
                 return
             except ValueError:
                 pass

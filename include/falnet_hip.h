@@ -241,9 +241,13 @@ typedef struct {
                                   0 = gC */
     int32_t up2;               /* variant 7 only, else 0.  != 0: the weight gradient of a `deconv` layer (nearest 2x upsampling + 3x3 convolution,
                                   FAL_netB.py:52-58) on the LOW-resolution grid: `gout` is the upstream gradient at [B][2 TH][2 TW][gC], the one source
-                                  the layer's input at TH x TW (= IH x IW); nsplit = 4 x pixel ranges (split = 4 range + 2 py + px): a split multiplies
-                                  the gout pixels of its parity class with the 2 x 2 input offsets they meet (16 instead of 36 tap products per
-                                  position) and writes its share of the full 3x3 slab, so the slab reduce is unchanged */
+                                  the layer's input at TH x TW (= IH x IW); 16 instead of 36 tap products per low-resolution position, and every
+                                  workgroup writes its share of the full 3x3 slab, so the slab reduce is unchanged.
+                                  1: nsplit = 4 x pixel ranges (split = 4 range + 2 py + px): a split multiplies the gout pixels of ONE parity
+                                  class with the 2 x 2 input offsets they meet; every class walks the whole grid (wgrad3x3_rows16_kernel<T,4,2,true>).
+                                  2: nsplit = pixel ranges of (sample, 32-column strip, low-resolution row) units, any count >= 1: a row step
+                                  carries two low-resolution rows and ALL FOUR parity classes of gout, a quarter of the high-resolution form's
+                                  steps with the input fetched once (wgrad3x3_up2q_kernel<T,2>) */
 } falnet_wgrad_t;
 /* 1 when the kernel falnet_wgrad selects for this descriptor sums the bias gradient itself (bias_grad honoured), else 0 */
 int falnet_wgrad_fuses_bias(const falnet_wgrad_t* p);

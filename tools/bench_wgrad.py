@@ -55,10 +55,12 @@ for name, groups, cout, H, W, up in LAYERS:
             ops._WGRAD_ROWS_WGS = wgs
             c = ops.wgrad_calls(dtype, srcs, up[0], up[1], gout, taps, 1, B, up[0], up[1], pc, gw, None, ws, up2=True)
             cands.append((f"lowres{wgs} n{c.desc.nsplit}", c))
+            c = ops.wgrad_calls(dtype, srcs, up[0], up[1], gout, taps, 1, B, up[0], up[1], pc, gw, None, ws, up2=2)  # all four parity classes per row step
+            cands.append((f"quad{wgs} n{c.desc.nsplit}", c))
     flops = 2.0 * B * H * W * cout * cin * 9
     times = {k: [] for k, _ in cands}
     ref = None
-    for rnd in range(6):
+    for rnd in range(int(os.environ.get("BENCH_ROUNDS", "5")) + 1):
         for k, c in cands:
             lib, refd = L.lib(), c.desc
             def run():
@@ -90,6 +92,7 @@ for name, groups, cout, H, W, up in LAYERS:
     for k, _ in cands:
         t = sorted(times[k])[len(times[k]) // 2]
         tot[k.split()[0]] = tot.get(k.split()[0], 0.0) + t
-        line += f" | {k:16s} {t*1e3:6.1f}us {flops/t/1e9:6.0f}TF"
+        sd = (sum((v - sum(times[k]) / len(times[k])) ** 2 for v in times[k]) / max(1, len(times[k]) - 1)) ** 0.5  # scatter of the repeats
+        line += f" | {k:16s} {t*1e3:6.1f}us sd {sd*1e3:4.1f} {flops/t/1e9:6.0f}TF"
     print(line, flush=True)
 print("total ms:", {k: round(v, 3) for k, v in tot.items()})
