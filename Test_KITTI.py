@@ -112,6 +112,18 @@ parser.add_argument('--device-percentile', action='store_true', help="ms_pp's 95
                     'copy to the host and np.percentile')
 parser.add_argument('--device-metrics', action='store_true', help='KITTI depth errors (with -median too) and EPE from the device-side metric kernels '
                     '(fal_net_amd/metrics.py) into a table read once after the last frame, instead of two full-size copies and float64 numpy per frame')
+parser.add_argument('--view-metrics', action='store_true',
+                    help='also judge the synthesised right view against the real one: RMSE, MAE, PSNR and SSIM per frame from one more forward after the '
+                         'timed region, on the device (fal_net_amd/metrics.py: view_errors, ssim); writes view_errors.txt and one JSON line.  --synthetic '
+                         'has no real right image: the view is judged on a seeded stereo pair with known geometry (synthetic.structured_stereo)')
+
+
+def write_view_errors(path, view):
+    """view_errors.txt: the means over the frames of the synthesised view's errors against the real right image."""
+    with open(path, 'w') as f:
+        f.write('\nView synthesis over {} frames (8-bit units; SSIM: 11 x 11 Gaussian window, sigma 1.5)\n'.format(view['n']))
+        f.write('\n' + ''.join('{:>10s}'.format(k) for k in ('rmse', 'mea', 'psnr', 'ssim')) + '\n')
+        f.write(''.join('{:>10.4f}'.format(view[k]) for k in ('rmse', 'mea', 'psnr', 'ssim')) + '\n')
 
 
 def _sweep_count(v):
@@ -377,8 +389,11 @@ def main():
                                               max_height=args.pl_max_height, min_conf=args.pl_min_conf), source
 
     sparsification = None
+    view = None
 
     def extra_lines():
+        if view is not None:
+            print(json.dumps({'view': view, 'file': os.path.join(save_path, 'view_errors.txt')}))
         if sparsification is not None:
             print(json.dumps({'sparsification': {'scores': res['sparsification']['names'], 'steps': res['sparsification']['steps'],
                                                  'frames': res['sparsification']['frames'], 'ause': res['sparsification']['ause_mean'],
@@ -421,7 +436,10 @@ def main():
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
-                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification)
+                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics)
+        if args.view_metrics:
+            view = res['view']
+            write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
         if sparsification is not None:
             write_sparsification(os.path.join(save_path, 'sparsification.txt'), res['sparsification'])
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
@@ -465,6 +483,17 @@ def main():
             inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
         if lidar_writer is not None:
             inference.lidar_frame(lidar_writer, 0, pan_model, left, disp, min_disp, max_disp)
+        if args.view_metrics:
+            # the timed image is seeded noise and its pair's right image is independent of it: no view metric means anything there.  The view is
+            # judged on a seeded pair with real geometry instead (synthetic.structured_stereo: the right image IS the left one resampled along a
+            # smooth disparity field), at the same size: one more forward on the plan of the timed one
+            from fal_net_amd import metrics
+            s_left, s_right = synthetic.structured_stereo(1, args.height, args.width, seed=7)[:2]
+            view_table = metrics.MetricTable(1, dev)
+            inference.view_frame(view_table, pan_model, s_left.to(dev), s_right.to(dev), min_disp, max_disp)
+            view = inference.view_result(view_table)
+            os.makedirs(save_path, exist_ok=True)
+            write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
     extra_lines()
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))

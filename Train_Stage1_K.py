@@ -34,6 +34,9 @@ parser.add_argument('-mm', '--m_model', default='FAL_netB', choices=['FAL_netA',
 parser.add_argument('-no_levels', '--no_levels', type=int, default=49)
 parser.add_argument('-perc', '--a_p', type=float, default=0.01)
 parser.add_argument('-smooth', '--a_sm', type=float, default=0.2 * 2 / 512)
+parser.add_argument('-ssim', '--a_ssim', type=float, default=0.0,
+                    help='weight of the photometric SSIM term mean((1 - SSIM) / 2), 3 x 3 window, in the reconstruction loss of Stage 1 '
+                         '(fal_net_amd.loss_functions.ssim_loss); 0: the term and its kernel are not run')
 parser.add_argument('-w', '--workers', type=int, default=4)
 parser.add_argument('-b', '--batch_size', type=int, default=8)
 parser.add_argument('-ch', '--crop_height', type=int, default=192)
@@ -224,7 +227,7 @@ def main(step='stage1_step'):
                                         min_disp_arg=args.min_disp, max_disp_arg=args.max_disp)
             else:
                 out = getattr(train, step)(m_model, opt, left, right, mx, a_p=args.a_p, a_sm=args.a_sm,
-                                           min_disp_arg=args.min_disp, max_disp_arg=args.max_disp)
+                                           min_disp_arg=args.min_disp, max_disp_arg=args.max_disp, a_ssim=args.a_ssim)
             if i % args.print_freq == 0:
                 losses.update(float(out['loss']), args.batch_size)
                 rec_losses.update(float(out['rec']), args.batch_size)
@@ -236,6 +239,8 @@ def main(step='stage1_step'):
                            'pairs_per_s': world * args.batch_size * (i + 1) / (time.time() - end)}
                     if f16_scale is not None:
                         rec['f16_loss_scale'], rec['f16_skipped_steps'] = f16_scale
+                    if 'ssim' in out:
+                        rec['ssim_loss'] = float(out['ssim'])
                     if stage2:
                         rec['mirror'] = float(out['mirror'])
                     print(json.dumps(rec), flush=True)

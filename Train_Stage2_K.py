@@ -16,4 +16,6 @@ if __name__ == '__main__':
                              help='real-data run WITHOUT Stage-1 checkpoints: seeded (untrained) student and teacher -- tests only')
     base.parser.set_defaults(batch_size=4, lr=0.00005, milestones=[5, 10], epochs=20, a_sm=0.4 * 2 / 512)
     base.args = base.parser.parse_args()
+    if base.args.a_ssim != 0:  # the Stage-2 reconstruction loss is masked by the occlusion maps; a masked SSIM term is not built
+        base.parser.error('-ssim/--a_ssim is a Stage-1 term: Stage 2 masks its reconstruction loss and no masked SSIM is built (got {})'.format(base.args.a_ssim))
     base.main(step='stage2_step')

@@ -203,6 +203,11 @@ SIGNATURES = {
     "falnet_depth_errors": [_P, _P, _I, _I, _I, _D, _P, _D, _D, _P, _P, _P],
     "falnet_epe": [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     "falnet_view_errors": [_P, _P, _F, _F, _F, _I, _I, _I, _P, _P, _P],
+    "falnet_ssim_workspace_bytes": [_I, _I, _I, _I, _I],
+    "falnet_ssim_metric": [_P, _P, _F, _F, _F, _I, _I, _I, _P, _P, _P],
+    "falnet_ssim_loss_fwd": [_P, _P, _F, _F, _F, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P],
+    "falnet_ssim_loss_bwd": [_P, _P, _F, _F, _F, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P],
+    "falnet_ssim_loss_fwd_bwd": [_P, _P, _F, _F, _F, _I, _I, _I, _I, _I, _F, _P, _F, _P, _P, _I, _P, _P],
     "falnet_velo_project": [_P, _I, _P, _I, _I, _I, _P, _P],
     "falnet_lidar_workspace_bytes": [_I, _I, _I, _I],
     "falnet_velo_unproject": [_P, _D, _P, _F, _P, _F, _P, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
@@ -214,7 +219,7 @@ SIGNATURES = {
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
              "falnet_lidar_workspace_bytes": C.c_int64, "falnet_sort_u32_workspace_bytes": C.c_int64,
-             "falnet_sparsify_workspace_bytes": C.c_int64}
+             "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

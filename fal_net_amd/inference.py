@@ -106,6 +106,22 @@ def sparsify_frame(table, pan_model, left, disp, target, mode, use_median, min_d
     S.curves(disp, target, mode, S.score_maps(st, table.names), use_median=use_median, steps=table.steps, out=table.row(table.n))
 
 
+def view_frame(table, pan_model, left, right, min_disp, max_pix):
+    """One frame's synthesised right view against the real one into the next row of `table` (a metrics.MetricTable of the view's own): RMSE, MAE
+    and PSNR (metrics.view_errors) and SSIM (metrics.ssim), from one more forward with ret_pan=True."""
+    from . import metrics as M
+    p_im, _ = pan_model(left, min_disp, max_pix, ret_disp=True, ret_subocc=False, ret_pan=True)
+    row = table.row(table.n)
+    M.view_errors(p_im, right, out=row)
+    M.ssim(p_im, right, out=row)
+
+
+def view_result(table):
+    """{'rmse', 'mea', 'psnr', 'ssim': means over the frames, 'n'} of a view_frame table -- the one read of it."""
+    res = table.result()
+    return {"rmse": res["rmse_mean"], "mea": res["mea_mean"], "psnr": res["psnr_mean"], "ssim": res["ssim_mean"], "n": int(len(res["view"]))}
+
+
 def peak_disparity(pan_model, left, min_disp, max_pix):
     """The forward with the peak disparity (confidence.py: the expectation over the arg-max plane and its two neighbours) in the place of
     the expectation over all planes: one disparity-only forward and one statistics launch over its logits."""
@@ -115,7 +131,7 @@ def peak_disparity(pan_model, left, min_disp, max_pix):
 
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
-             sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None, sparsification=None):
+             sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None, sparsification=None, view_metrics=False):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -133,6 +149,9 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     sparsification: a sparsification.SparsificationTable built with the score names -- every frame with ground truth also leaves its sparsification
     curves in the table's next row (sparsify_frame: the errors of `disp` after post-processing, the scores from one more disparity-only forward), with
     and without device_metrics; the table is read once after the last frame and its result() is returned under 'sparsification'.
+    view_metrics: every frame with a right image also runs one more forward with ret_pan=True after the timed region, and the synthesised view's
+    RMSE / MAE / PSNR and SSIM against the loader's right image go into a device table of their own (view_frame), read once after the last frame; the
+    result gains 'view': {'rmse', 'mea', 'psnr', 'ssim', 'n'}.
     disparity: "mean" (the forward's expectation) or "peak" (peak_disparity; only with post == "none": ms_pp and the flip blend two expectations)."""
     if disparity not in ("mean", "peak"):
         raise ValueError("disparity must be 'mean' or 'peak', got {!r}".format(disparity))
@@ -150,6 +169,10 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     if device_metrics and with_metrics:
         from . import metrics as M
         table = M.MetricTable(len(loader.dataset) if hasattr(loader, "dataset") else 1, dev)
+    view_table = None
+    if view_metrics:
+        from . import metrics as M
+        view_table = M.MetricTable(len(loader.dataset) if hasattr(loader, "dataset") else 1, dev)
     with torch.no_grad():
         for i, batch in enumerate(loader):
             for left_u8, right_u8, gt in batch:
@@ -188,6 +211,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                         kitti.update(utils.compute_kitti_errors(gt_depth[0], pred_depth[0], use_median=use_median), 1)
                     if sparsification is not None:
                         sparsify_frame(sparsification, pan_model, left, disp, target, "kitti2015" if data_name == "Kitti2015" else "eigen", use_median, mn, mx)
+                if view_table is not None and right_u8 is not None:
+                    view_frame(view_table, pan_model, left, DS.to_model_input(right_u8, dev), mn, mx)
                 if writer is not None:
                     dump_frame(writer, n, pan_model, left, disp, mn, mx)
                 if sweep_writer is not None:
@@ -210,4 +235,6 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
            "sec_per_image": batch_time.avg}
     if sparsification is not None:
         out["sparsification"] = sparsification.result()
+    if view_table is not None:
+        out["view"] = view_result(view_table)
     return out

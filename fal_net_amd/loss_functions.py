@@ -329,6 +329,49 @@ class _L1Mean(torch.autograd.Function):
         return ga, None, None, None
 
 
+class _SsimLoss(torch.autograd.Function):
+    """mean((1 - SSIM) / 2) over the valid 3 x 3 windows of synth + mean against label + mean (csrc/ssim.hip); gradient wrt synth only."""
+
+    @staticmethod
+    def forward(ctx, synth, label, mean):
+        B, C, H, W = synth.shape
+        a, b = synth.contiguous(), label.contiguous()
+        lib = L.lib()
+        out = torch.empty(1, device=synth.device)
+        ws = torch.empty(max(int(lib.falnet_ssim_workspace_bytes(B, C, H, W, 1)) // 8, 1), dtype=torch.int64, device=synth.device)
+        sc = 1.0 / (B * C * max(H - 2, 1) * max(W - 2, 1))  # (an image smaller than one window: the kernel's argument error)
+        L.check(lib.falnet_ssim_loss_fwd(L.ptr(a), L.ptr(b), mean[0], mean[1], mean[2], B, C, H, W, 1, sc, L.ptr(out), 0, L.ptr(ws), L.stream_ptr()),
+                "ssim_loss_fwd")
+        ctx.save_for_backward(a, b)
+        ctx.sc, ctx.mean = sc, mean
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        B, C, H, W = a.shape
+        ga = torch.empty_like(a)
+        gs = g.reshape(1).contiguous().float()
+        m = ctx.mean
+        L.check(L.lib().falnet_ssim_loss_bwd(L.ptr(a), L.ptr(b), m[0], m[1], m[2], B, C, H, W, 1, ctx.sc, L.ptr(gs), L.ptr(ga), 0, L.stream_ptr()),
+                "ssim_loss_bwd")
+        return ga, None, None
+
+
+def ssim_loss(synth, label, window=3, mean=_MEAN):
+    """The photometric SSIM term of Monodepth: mean((1 - SSIM(synth + mean, label + mean)) / 2) with the 3 x 3 box window, C1 = 0.01^2,
+    C2 = 0.03^2, over the (H - 2) x (W - 2) valid windows of every plane, f32.  synth, label: (B, C <= 3, H, W) f32 on the GPU, normalised by
+    `mean` (SSIM is not shift-invariant: the loader's mean goes back on).  Gradient with respect to synth only.  Only window = 3 is built."""
+    if window != 3:
+        raise ValueError("ssim_loss: only the 3 x 3 window is built, got window = {!r}".format(window))
+    if not synth.is_cuda:
+        raise RuntimeError("fal_net_amd ssim_loss runs on an MI355X only (no CPU fallback)")
+    if synth.dim() != 4 or synth.shape != label.shape or synth.shape[1] > 3:
+        raise ValueError("ssim_loss: expected two (B, C <= 3, H, W) images, got {} and {}".format(tuple(synth.shape), tuple(label.shape)))
+    m = tuple(float(v) for v in mean) + (0.0, 0.0)
+    return _SsimLoss.apply(synth.float(), label.detach().float(), m[:3])
+
+
 def occlusion_mask(a, b, x0, x1):
     """Stage-2 occlusion mask (Train_Stage2_K.py:296-302): a * b with the column window [x0, x1) forced to 1; no gradient."""
     B, _, H, W = a.shape

@@ -18,9 +18,10 @@ MEAN = (0.411, 0.432, 0.45)  # Train_Stage1_K.py:127 -- what the loader subtract
 MODES = {"kitti2015": 0, "eigen": 1, "make3d": 2}  # FALNET_DEPTH_* of include/falnet_hip.h
 ROW = 24  # FALNET_MET_ROW; the columns (FALNET_MET_*):
 COLUMNS = ("abs_rel", "sq_rel", "rms", "log_rms", "a1", "a2", "a3", "n", "n_a1", "n_a2", "n_a3", "scale", "median_gt", "median_pred",
-           "epe", "epe_n", "rmse", "mea", "psnr", "view_sum_sq", "view_sum_abs", "view_sum_rsq", "view_n", "reserved")
+           "epe", "epe_n", "rmse", "mea", "psnr", "view_sum_sq", "view_sum_abs", "view_sum_rsq", "view_n", "ssim")
 COL = {name: i for i, name in enumerate(COLUMNS)}
 _GROUP_COLUMN = {"depth": COL["n"], "epe": COL["epe_n"], "view": COL["view_n"]}  # a group's count column: NaN until the group is written
+# ('ssim' is a group of one column, written by csrc/ssim.hip: MetricTable.result() filters it on the column itself)
 
 
 def focal_baseline(mode, width):
@@ -74,6 +75,12 @@ class MetricTable:
         self.workspace = torch.empty(int(L.lib().falnet_metrics_workspace_bytes()) // 8, dtype=torch.int64, device=self.device)
         self.scale = torch.empty(4, dtype=torch.float64, device=self.device)  # {factor, median gt, median pred, n}: select -> error kernel
         self.n = 0  # rows handed out
+        self._ssim_ws = None  # partial sums of csrc/ssim.hip: one word per tile of the largest frame so far
+
+    def ssim_workspace(self, nbytes):
+        if self._ssim_ws is None or self._ssim_ws.numel() * 8 < nbytes:
+            self._ssim_ws = torch.empty(max((int(nbytes) + 7) // 8, 1), dtype=torch.int64, device=self.device)
+        return self._ssim_ws
 
     def row(self, i):
         if i >= self.table.shape[0]:  # a loader of unknown length: double, on the device (no host read)
@@ -92,20 +99,24 @@ class MetricTable:
         rows = self.rows()
         col = COL[column] if isinstance(column, str) else column
         group = "depth" if col < COL["epe"] else ("epe" if col < COL["rmse"] else "view")
-        vals = rows[~np.isnan(rows[:, _GROUP_COLUMN[group]]), col]
+        vals = rows[~np.isnan(rows[:, col if col == COL["ssim"] else _GROUP_COLUMN[group]]), col]
         return float(np.mean(vals)) if len(vals) else 0.0
 
     def result(self, make3d=False):
         """{'rows': (n, ROW) array, 'names': the seven depth names, 'depth' / 'epe' / 'view': per-frame rows of each group that was written
-        (frames in order), 'depth_mean', 'epe_mean', 'rmse_mean', 'mea_mean', 'psnr_mean': their means over those frames}.  A group never
-        written has no rows and a mean of 0, like an AverageMeter that was never updated."""
+        (frames in order), 'depth_mean', 'epe_mean', 'rmse_mean', 'mea_mean', 'psnr_mean': their means over those frames, 'ssim': the SSIM of
+        the frames it was written for (in order), 'ssim_mean'}.  A group never written has no rows and a mean of 0, like an AverageMeter that
+        was never updated."""
         rows = self.rows()
         written = {g: ~np.isnan(rows[:, c]) for g, c in _GROUP_COLUMN.items()}  # the count column is a finite number once a group is written
         depth, epe, view = rows[written["depth"]][:, :7], rows[written["epe"]][:, COL["epe"]], rows[written["view"]][:, COL["rmse"]:COL["psnr"] + 1]
         mean = lambda a: a.mean(0) if len(a) else np.zeros(a.shape[1:])
         vm = mean(view)
+        ssim_col = rows[:, COL["ssim"]]
+        ssim_vals = ssim_col[~np.isnan(ssim_col)]
         return {"rows": rows, "names": list(make_error_names if make3d else kitti_error_names), "depth": depth, "epe": epe, "view": view,
-                "depth_mean": mean(depth), "epe_mean": float(mean(epe)), "rmse_mean": float(vm[0]), "mea_mean": float(vm[1]), "psnr_mean": float(vm[2])}
+                "depth_mean": mean(depth), "epe_mean": float(mean(epe)), "rmse_mean": float(vm[0]), "mea_mean": float(vm[1]), "psnr_mean": float(vm[2]),
+                "ssim": ssim_vals, "ssim_mean": float(mean(ssim_vals))}
 
 
 def _out(out, device):
@@ -178,4 +189,20 @@ def view_errors(p_im, right, mean=MEAN, out=None):
     B, _, H, W = x.shape
     L.check(L.lib().falnet_view_errors(L.ptr(x), L.ptr(y), float(mean[0]), float(mean[1]), float(mean[2]), B, H, W, L.ptr(row.tensor),
                                        L.ptr(row.table.workspace), L.stream_ptr()), "view_errors")
+    return row.tensor
+
+
+def ssim(p_im, right, mean=MEAN, out=None):
+    """Structural similarity (Wang et al. 2004: 11 x 11 Gaussian window of sigma 1.5, valid windows, data range 255) of the synthesised view p_im
+    against the real one, both (B, 3, H, W) normalised by `mean`, on get_psnr's operands round(clamp(255 (p_im + mean), 0, 255)) and 255 (right +
+    mean); window sums in f64 on the device -> the row's tensor (column 'ssim': the mean over the B * 3 * (H - 10) * (W - 10) windows)."""
+    x, y = _map(p_im, "p_im"), _map(right, "right")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape != y.shape:
+        raise ValueError("ssim: expected two (B, 3, H, W) images, got {} and {}".format(tuple(x.shape), tuple(y.shape)))
+    row = _out(out, x.device)
+    B, _, H, W = x.shape
+    lib = L.lib()
+    ws = row.table.ssim_workspace(lib.falnet_ssim_workspace_bytes(B, 3, H, W, 5))  # (a frame too small for one window: the kernel's error below)
+    L.check(lib.falnet_ssim_metric(L.ptr(x), L.ptr(y), float(mean[0]), float(mean[1]), float(mean[2]), B, H, W, L.ptr(row.tensor), L.ptr(ws),
+                                   L.stream_ptr()), "ssim_metric")
     return row.tensor

@@ -89,6 +89,13 @@ def get_psnr(output_right, label_right, mean=(0.411, 0.432, 0.45)):
     return torch.mean(20 * torch.log10(255 / rmse))
 
 
+def get_ssim(output_right, label_right, mean=(0.411, 0.432, 0.45)):
+    """SSIM of the synthesised view on get_psnr's operands (Wang et al. 2004: 11 x 11 Gaussian window, data range 255), computed by the SSIM kernel
+    (fal_net_amd.metrics.ssim; no host form) -> a float64 scalar on the input's device."""
+    from . import metrics
+    return metrics.ssim(output_right, label_right, mean=mean)[metrics.COL["ssim"]]
+
+
 def get_point_cloud(img, disp):
     """myUtils.py:339-373: `img` is RGB in 0..255, `disp` in pixels -> (B, 6, H W) rows x, z, -y, r, g, b on the input's device, computed by
     the point-cloud kernel (fal_net_amd.dumps.point_cloud).  KeyError on a width that is not a KITTI width, as in the reference."""

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
-from .loss_functions import mirror_loss_fnc, occlusion_mask, rec_loss_fnc, smoothness, vgg
+from .loss_functions import mirror_loss_fnc, occlusion_mask, rec_loss_fnc, smoothness, ssim_loss, vgg
 
 
 import os as _os
@@ -399,7 +399,7 @@ def _seed(device, value):
     return _SEEDS[key]
 
 
-def _stage1_fused(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize):
+def _stage1_fused(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize, a_ssim=0.0):
     """The same iteration as `stage1_step`'s autograd form, as a static launch sequence: the plan's forward, the loss kernels
     accumulating into one device scalar pair, their adjoints seeded by cached device scalars and writing straight into the
     plans' gradient buffers, the plan's backward.  No autograd graph, no scalar aten launches (the autograd form spends ~30
@@ -407,7 +407,7 @@ def _stage1_fused(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, ma
     `ldisp` in the result alias the plan's output buffers: valid until the model's next forward of this shape."""
     with L.stream_scope():  # one stream lookup for the ~330 launches of the step
         try:
-            return _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize)
+            return _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize, a_ssim)
         except BaseException:
             # the loss accumulators are zero on entry by contract (falnet_step_scalars re-zeroes them at the END of a step): a step that
             # fails in between must not leave its partial sums for the next one
@@ -429,7 +429,7 @@ def _mark(marks):
         marks.append(e)
 
 
-def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize):
+def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize, a_ssim=0.0):
     from . import loss_functions as LF
     lib = L.lib()
     marks = None if PHASE_MARKS is None else []
@@ -442,9 +442,11 @@ def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_ar
     scaler = loss_scaler(model)
     if scaler is None:
         seed_l1, seed_p, seed_sm = _seed(dev, 1.0), _seed(dev, a_p), _seed(dev, a_sm)
-    else:  # f16: the upstream scalars carry the device-resident loss scale
-        sd3 = scaler.seeds(1.0, a_p, a_sm)
+        seed_ssim = _seed(dev, a_ssim) if a_ssim > 0 else None
+    else:  # f16: the upstream scalars carry the device-resident loss scale (the key grows only with the SSIM term: the default one stays)
+        sd3 = scaler.seeds(1.0, a_p, a_sm, a_ssim) if a_ssim > 0 else scaler.seeds(1.0, a_p, a_sm)
         seed_l1, seed_p, seed_sm = sd3[0:], sd3[1:], sd3[2:]
+        seed_ssim = sd3[3:] if a_ssim > 0 else None
     joins = []
     if a_p > 0:
         if L.ab("FALNET_LABEL_VGG_MID", "1") == "1" and ops.TIMER is None:
@@ -510,12 +512,24 @@ def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_ar
         L.check(lib.falnet_l1_fwd_bwd_add(L.ptr(rpan), L.ptr(rt), B, C, H * W, 1.0 / n_img, L.ptr(S), L.ptr(seed_l1), L.ptr(vplan.g_in), L.ptr(g_pan), st),
                 "l1_fwd_bwd_add")
         vplan.busy = False
+    ssim_ws = None
+    if a_ssim > 0:  # the SSIM term joins rec and the gradient of the synthesised view that the L1 kernel has just written
+        nb = int(lib.falnet_ssim_workspace_bytes(B, C, H, W, 1))
+        ssim_ws = b.get("ssim_ws")
+        if ssim_ws is None or ssim_ws.numel() * 8 < nb:
+            ssim_ws = b["ssim_ws"] = torch.zeros(max(nb // 8, 1), dtype=torch.float64, device=dev)
+        n_win = B * C * max(H - 2, 1) * max(W - 2, 1)
+        m = LF._MEAN
+        L.check(lib.falnet_ssim_loss_fwd_bwd(L.ptr(rpan), L.ptr(rt), m[0], m[1], m[2], B, C, H, W, 1, a_ssim / n_win, L.ptr(S), 1.0 / n_win,
+                                             L.ptr(seed_ssim), L.ptr(g_pan), 1, L.ptr(ssim_ws), st), "ssim_loss_fwd_bwd")
     _mark(marks)
     plan.run_backward(g_disp if a_sm > 0 else None, g_pan, in_place=True)
     _mark(marks)
     Sc = torch.empty(3, device=dev)  # a fresh triple per step (callers keep loss tensors across steps); no launch: caching allocator
     L.check(lib.falnet_step_scalars(L.ptr(S), float(a_sm), L.ptr(Sc), st), "step_scalars")  # {rec + a_sm sm, rec, sm}; S -> 0
     out = {"loss": Sc[0], "rec": Sc[1], "sm": Sc[2] if a_sm > 0 else 0, "rpan": rpan, "ldisp": ldisp, "scaler": scaler}
+    if ssim_ws is not None:  # the term by itself: the sum the finalising kernel left in the workspace's last word, over the windows
+        out["ssim"] = (ssim_ws[nb // 8 - 1] / n_win).float()
     if optimize:
         opt.step(allreduce_gradients(model), scaler=scaler)
     _mark(marks)
@@ -525,14 +539,15 @@ def _stage1_fused_body(model, opt, left, right, max_disp, a_p, a_sm, min_disp_ar
 
 
 def stage1_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 / 512, min_disp_arg=2.0, max_disp_arg=300.0,
-                optimize=True):
+                optimize=True, a_ssim=0.0):
     """One iteration of Train_Stage1_K.py:233-262 (forward, VGG, losses, backward, all-reduce, Adam).
-    Returns device scalars (no host sync)."""
+    Returns device scalars (no host sync).  a_ssim > 0 adds the photometric SSIM term (loss_functions.ssim_loss) to the reconstruction loss:
+    rec = L1 + a_p * perceptual + a_ssim * ssim; the result then carries 'ssim'.  With a_ssim = 0 the step issues the launches it always did."""
     opt.zero_grad()
     enable_overlapped_allreduce(model)
     if (_FUSED_STEP and left.is_cuda and torch.is_grad_enabled() and hasattr(model, "_plan")
             and all(p.requires_grad for _, p in model._trainable_named())):
-        return _stage1_fused(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize)
+        return _stage1_fused(model, opt, left, right, max_disp, a_p, a_sm, min_disp_arg, max_disp_arg, optimize, a_ssim)
     W = left.shape[3]
     min_disp = max_disp * min_disp_arg / max_disp_arg  # :237
     # :241-244 label features, overlapped with the model forward: started from the plan's mid-forward hook, i.e. when the
@@ -549,6 +564,10 @@ def stage1_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 / 512,
         joins.append(vgg_label_async(right))
     vgg_right = joins[0]() if joins else None
     rec_loss = rec_loss_fnc(1, rpan, right, vgg_right, a_p)  # :248
+    ssim_term = None
+    if a_ssim > 0:
+        ssim_term = ssim_loss(rpan, right)
+        rec_loss = rec_loss + a_ssim * ssim_term
     sm_loss = 0
     if a_sm > 0:
         c = int(0.20 * W)
@@ -557,13 +576,15 @@ def stage1_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 / 512,
     sc = scaled_backward(loss, model)
     out = {"loss": loss.detach(), "rec": rec_loss.detach(), "sm": sm_loss.detach() if torch.is_tensor(sm_loss) else sm_loss,
            "rpan": rpan, "ldisp": ldisp, "scaler": sc}
+    if ssim_term is not None:
+        out["ssim"] = ssim_term.detach()
     if optimize:
         opt.step(allreduce_gradients(model), scaler=sc)
     return out
 
 
 def stage1_slow_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 / 512, min_disp_arg=2.0,
-                     max_disp_arg=300.0):
+                     max_disp_arg=300.0, a_ssim=0.0):
     """One iteration of Train_Stage1_Kslow.py:236-284: both views in one 2B batch (left | flip(right)), the second
     half of the outputs flipped back, reconstruction and smoothness averaged over the two views."""
     opt.zero_grad()
@@ -577,6 +598,10 @@ def stage1_slow_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 /
     ldisp, rdisp = disp[0:B], flip(disp[B:])
     vgg_right, vgg_left = (joins[0](), joins[1]()) if joins else (None, None)
     rec_loss = (rec_loss_fnc(1, rpan, right, vgg_right, a_p) + rec_loss_fnc(1, lpan, left, vgg_left, a_p)) / 2  # :268-269
+    ssim_term = None
+    if a_ssim > 0:  # the SSIM term of both views, averaged like the reconstruction loss it joins
+        ssim_term = (ssim_loss(rpan, right) + ssim_loss(lpan, left)) / 2
+        rec_loss = rec_loss + a_ssim * ssim_term
     sm_loss = 0
     if a_sm > 0:  # :274-278
         c2, c8 = int(0.20 * W), int(0.80 * W)
@@ -585,8 +610,11 @@ def stage1_slow_step(model, opt, left, right, max_disp, a_p=0.01, a_sm=0.2 * 2 /
     loss = rec_loss + a_sm * sm_loss  # :281
     sc = scaled_backward(loss, model)
     opt.step(allreduce_gradients(model), scaler=sc)
-    return {"loss": loss.detach(), "rec": rec_loss.detach(), "sm": sm_loss.detach() if torch.is_tensor(sm_loss) else sm_loss,
-            "rpan": rpan, "lpan": lpan, "ldisp": ldisp, "rdisp": rdisp, "scaler": sc}
+    out = {"loss": loss.detach(), "rec": rec_loss.detach(), "sm": sm_loss.detach() if torch.is_tensor(sm_loss) else sm_loss,
+           "rpan": rpan, "lpan": lpan, "ldisp": ldisp, "rdisp": rdisp, "scaler": sc}
+    if ssim_term is not None:
+        out["ssim"] = ssim_term.detach()
+    return out
 
 
 class GraphedStage1Step:
@@ -625,7 +653,8 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
     """Train_Stage1_K.py:279-347 / Train_Stage2_K.py validate(): full-size forward (disp + synthesised right view + masks), RMSE of
     the synthesised view, EPE and the KITTI depth errors against the ground-truth disparity.  `val_loader` yields lists of
     (left_u8, right_u8, disp) from fal_net_amd.datasets.StereoValDataset (batch size 1 in the reference, :152).
-    Returns {'rmse', 'epe', 'kitti': {name: value}} (the reference returns the RMSE, :345).
+    Returns {'rmse', 'epe', 'kitti': {name: value}, 'ssim'} (the reference returns the RMSE, :345); 'ssim' is the mean over the frames of the
+    synthesised view's structural similarity (metrics.ssim: the kernel runs in both modes, there is no host form).
     device_metrics: the three numbers of a frame come from the kernels behind fal_net_amd/metrics.py into a device-resident table that is read
     after the last frame (and on the iterations that print): no per-frame copy of a map or a metric to the host."""
     import numpy as np
@@ -636,9 +665,10 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
     was_training = model.training
     model.eval()
     rmses, epes, kitti = utils.AverageMeter(), utils.AverageMeter(), utils.multiAverageMeter(utils.kitti_error_names)
-    table = None
+    ssims = utils.AverageMeter()
+    table, ssim_vals = None, []
+    from . import metrics as M
     if device_metrics:
-        from . import metrics as M
         table = M.MetricTable(len(val_loader.dataset) if hasattr(val_loader, "dataset") else 1, dev)
     with torch.no_grad():
         for i, batch in enumerate(val_loader):
@@ -650,12 +680,14 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
                 if table is not None:
                     row = table.row(table.n)
                     M.view_errors(p_im, right, out=row)
+                    M.ssim(p_im, right, out=row)
                     if disp_gt is not None:
                         target = disp_gt.to(dev).view(1, 1, *disp_gt.shape)
                         M.epe(disp, target, sparse=sparse, out=row)
                         M.depth_errors(disp, target, "kitti2015", out=row)
                     continue
                 rmses.update(float(utils.get_rmse(p_im, right)))
+                ssim_vals.append(utils.get_ssim(p_im, right))  # a device scalar: read with the others after the loop
                 if disp_gt is not None:
                     target = disp_gt.to(dev).view(1, 1, *disp_gt.shape)
                     epes.update(float(realEPE(disp, target, sparse=sparse)), 1)
@@ -671,8 +703,13 @@ def validate(model, val_loader, max_disp=300.0, min_disp=2.0, rel_baset=1.0, spa
             epes.update(float(e), 1)
         for errs in res["depth"]:
             kitti.update(errs, 1)
+        ssim_vals = list(res["ssim"])
+    elif ssim_vals:
+        ssim_vals = torch.stack(ssim_vals).cpu().tolist()
+    for v in ssim_vals:
+        ssims.update(float(v))
     model.train(was_training)
-    return {"rmse": rmses.avg, "epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg]))}
+    return {"rmse": rmses.avg, "epe": epes.avg, "kitti": dict(zip(utils.kitti_error_names, [float(a) for a in kitti.avg])), "ssim": ssims.avg}
 
 
 def hflip(x):

@@ -682,6 +682,7 @@ int falnet_point_cloud(const float* img, float mean_r, float mean_g, float mean_
 #define FALNET_MET_VIEW_SUM_ABS 20
 #define FALNET_MET_VIEW_SUM_RSQ 21
 #define FALNET_MET_VIEW_N 22
+#define FALNET_MET_SSIM 23 /* structural similarity of the view (falnet_ssim_metric, csrc/ssim.hip): a group of its own, NaN until written */
 int64_t falnet_metrics_workspace_bytes(void);
 /* np.median(gt[mask]) / np.median(pred[mask]) of the depths of one frame (H x W f32 maps; `mode` and `fb` = focal * baseline as below), exact:
  * a radix select over the f64 depths with a 64-bit key, the number of selected pixels and the ranks found on the device; an even count takes the
@@ -702,6 +703,33 @@ int falnet_epe(const float* pred, int h, int w, const float* target, int B, int 
  * 255), lab = 255 (y + mean) in f32; sums of (out - lab)^2, |out - lab| and (round(out) - lab)^2 in f64 */
 int falnet_view_errors(const float* out, const float* label, float mean_r, float mean_g, float mean_b, int B, int H, int W, double* row, void* workspace,
                        void* stream);
+
+/* ---- structural similarity (csrc/ssim.hip; Wang et al. 2004) ------------------------------------------------------------------------------
+ * For a plane pair x, y and a window w of radius R (the outer product of 1-D weights of sum 1), at every VALID window centre (no padding:
+ * (H - 2R) x (W - 2R) of them): mx = sum w x, my = sum w y, vx = sum w x^2 - mx^2, vy likewise, cxy = sum w x y - mx my,
+ * S = (2 mx my + C1)(2 cxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)).  One workgroup per tile of one plane; per-workgroup partial sums in the
+ * caller's workspace (falnet_ssim_workspace_bytes(B, C, H, W, radius) bytes, 8-byte aligned, owned by one stream at a time; 0 for a radius that is
+ * not built), added by a finalising kernel in a fixed order: no floating-point atomics, two calls give the same bits.  The workspace's LAST 8 bytes
+ * receive the plain sum over the windows as a double (of S for the metric, of (1 - S) / 2 for the loss).  H < 2R + 1 or W < 2R + 1 is an argument
+ * error.  None of these is replayable. */
+int64_t falnet_ssim_workspace_bytes(int B, int C, int H, int W, int radius);
+/* The metric: R = 5, Gaussian weights of sigma 1.5, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, on get_psnr's operands x = round(clamp((out + mean) * 255,
+ * 0, 255)), y = (label + mean) * 255 formed in f32 without a fused multiply-add; window sums and everything after them in f64.
+ * row[FALNET_MET_SSIM] = the mean of S over the B * 3 * (H - 10) * (W - 10) windows; no other column is touched.  out, label: (B, 3, H, W). */
+int falnet_ssim_metric(const float* out, const float* label, float mean_r, float mean_g, float mean_b, int B, int H, int W, double* row, void* workspace,
+                       void* stream);
+/* The loss: the 3 x 3 box (radius 1, the only one built: any other radius is an argument error), C1 = 0.01^2, C2 = 0.03^2, x = synth + mean_c,
+ * y = label + mean_c (C <= 3 channels), all f32:  out[0] (+)= scale * sum over the windows of (1 - S) / 2  (scale = 1 / (B C (H - 2)(W - 2)): the mean). */
+int falnet_ssim_loss_fwd(const float* synth, const float* label, float mean_r, float mean_g, float mean_b, int B, int C, int H, int W, int radius,
+                         float scale, float* out, int accumulate, void* workspace, void* stream);
+/* ga (+)= gscale[0] * scale * d sum((1 - S) / 2) / d synth (gscale NULL: 1); every element of ga is written, the border pixels that fewer windows
+ * contain included.  Needs no workspace. */
+int falnet_ssim_loss_bwd(const float* synth, const float* label, float mean_r, float mean_g, float mean_b, int B, int C, int H, int W, int radius,
+                         float scale, const float* gscale, float* ga, int accumulate, void* stream);
+/* Both in one launch: out[0] += scale_out * sum (as falnet_ssim_loss_fwd with accumulate = 1); ga = (add_grad ? ga : 0) + gscale[0] * scale_grad * d sum /
+ * d synth (as falnet_ssim_loss_bwd) -- add_grad = 1 joins the gradient another loss kernel has already written for the same tensor. */
+int falnet_ssim_loss_fwd_bwd(const float* synth, const float* label, float mean_r, float mean_g, float mean_b, int B, int C, int H, int W, int radius,
+                             float scale_out, float* out, float scale_grad, const float* gscale, float* ga, int add_grad, void* workspace, void* stream);
 
 /* ---- Velodyne ground truth (csrc/velo.hip; the original Eigen split, Datasets/Kitti_eigen_test_original.py) -----------------------------------
  * Monodepth's generate_depth_map of one raw KITTI scan on the device.  points: n_points x 4 f32 (x, y, z, reflectance) as the .bin file holds them,
