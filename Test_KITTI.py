@@ -13,6 +13,7 @@ Two modes:
   * `--synthetic`: seeded image of `--height x --width` (native KITTI 375x1242 by default), timing only -- no dataset on the box.
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
 (:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
+`--freeview V [--freeview-path orbit|dolly|pan]` adds V free-viewpoint views per frame, fal_net_amd/freeview.py;
 `--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
 `--stats KINDS` adds maps of the per-pixel disparity distribution (spread, entropy, arg-max plane, peak mass, peak disparity),
 `--pc-min-conf C` keeps only the confident vertices of the point cloud and `--disparity peak` evaluates the peak disparity, fal_net_amd/confidence.py;
@@ -138,6 +139,38 @@ parser.add_argument('--sweep', type=_sweep_count, default=None, metavar='V',
                          'fused launch per 8 views) into Sweep/<frame>_v<view>.png, and the disparity in the right view\'s own frame into r_disp/<frame>.png')
 parser.add_argument('--sweep-range', type=float, nargs=2, default=[-1.0, 1.0], metavar=('LO', 'HI'),
                     help='first and last baseline fraction of --sweep: 0 is the left camera, 1 the right one; |t| <= 2')
+
+
+def _freeview_count(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError('--freeview needs at least one pose, got {}'.format(n))
+    return n
+
+
+parser.add_argument('--freeview', type=_freeview_count, default=None, metavar='V',
+                    help='also render V free-viewpoint views per frame along --freeview-path from the frame\'s logits (fal_net_amd/freeview.py: a homography '
+                         'plane sweep, one launch per 8 poses, around the nominal camera of the frame\'s size) into Freeview/<frame>_p<pose>.png with the '
+                         'coverage maps Freeview/<frame>_p<pose>_cover.png, and one JSON line with the mean cover')
+parser.add_argument('--freeview-path', default='orbit', choices=['orbit', 'dolly', 'pan'],
+                    help='--freeview: orbit circles the left camera in its image plane (radii X, Y of --freeview-amp, toed in by --freeview-yaw), dolly moves '
+                         'forward from 0 to Z, pan turns on the spot from -DEG to DEG')
+parser.add_argument('--freeview-amp', type=float, nargs=3, default=[0.5, 0.25, 0.5], metavar=('X', 'Y', 'Z'), help='--freeview: amplitudes of the path in baselines')
+parser.add_argument('--freeview-yaw', type=float, default=3.0, metavar='DEG', help='--freeview: yaw amplitude of the path in degrees')
+FREEVIEW_ARGS = ('freeview', 'freeview_path', 'freeview_amp', 'freeview_yaw')
+
+
+def freeview_poses(a):
+    """The --freeview path as freeview.pose keyword sets (V of them), or None without --freeview."""
+    if a.freeview is None:
+        return None
+    from fal_net_amd.freeview import paths
+    x, y, z = a.freeview_amp
+    if a.freeview_path == 'orbit':
+        return paths.orbit(a.freeview, x, y, yaw=a.freeview_yaw)
+    if a.freeview_path == 'dolly':
+        return paths.dolly(a.freeview, 0.0, z)
+    return paths.pan(a.freeview, -a.freeview_yaw, a.freeview_yaw)
 
 
 STATS_KINDS = ('std', 'entropy', 'arg', 'conf', 'peak')
@@ -372,6 +405,16 @@ def main():
             raise SystemExit('--sweep-range: {}'.format(e))
         sweep_writer = dumps.SweepWriter(save_path)
 
+    fv_poses, freeview_writer = freeview_poses(args), None
+    if fv_poses is not None:
+        from fal_net_amd import freeview
+        try:
+            K = freeview.camera(args.height, args.width)
+            freeview.check_poses([freeview.pose(K, **kw) for kw in fv_poses])
+        except ValueError as e:
+            raise SystemExit('--freeview: {}'.format(e))
+        freeview_writer = freeview.FreeviewWriter(save_path)
+
     stats_writer = None
     if args.stats is not None or args.pc_min_conf is not None:
         from fal_net_amd import confidence
@@ -402,6 +445,9 @@ def main():
             print(json.dumps({'pseudo_lidar': dict(lidar_writer.summary(), calibration=lidar_source)}))
         if sweep_writer is not None:
             print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
+        if freeview_writer is not None:
+            print(json.dumps({'freeview': dict(freeview_writer.summary(), poses=args.freeview, path=args.freeview_path, amp=list(args.freeview_amp),
+                                               yaw=args.freeview_yaw, camera='nominal')}))
         if stats_writer is not None:
             print(json.dumps({'stats': stats_writer.summary()}))
 
@@ -425,6 +471,7 @@ def main():
                                                                                   ('stats', 'pc_min_conf', 'disparity'))
             hidden += () if args.pseudo_lidar else LIDAR_ARGS
             hidden += () if args.sparsification is not None else SPARSIFICATION_ARGS
+            hidden += () if args.freeview is not None else FREEVIEW_ARGS
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         if args.pseudo_lidar:
@@ -436,7 +483,8 @@ def main():
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
-                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics)
+                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics,
+                                 freeview_writer=freeview_writer, freeview_poses=fv_poses)
         if args.view_metrics:
             view = res['view']
             write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
@@ -479,6 +527,8 @@ def main():
             inference.dump_frame(writer, 0, pan_model, left, disp, min_disp, max_disp)
         if sweep_writer is not None:
             inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
+        if freeview_writer is not None:
+            inference.freeview_frame(freeview_writer, 0, pan_model, left, min_disp, max_disp, fv_poses)
         if stats_writer is not None:
             inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
         if lidar_writer is not None:

@@ -151,6 +151,7 @@ SIGNATURES = {
     "falnet_med_masks_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_maskr_acfalse_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_sweep_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P],
+    "falnet_med_pose_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_stats_fwd": [_P, _P, _P, C.c_uint, _P, _I, _I, _I, _I, _P],
     "falnet_compact_workspace_bytes": [_L],
     "falnet_compact_records": [_P, _I, _P, _F, _L, _P, _P, _P, _P],

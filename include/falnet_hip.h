@@ -420,6 +420,28 @@ int falnet_med_maskr_acfalse_fwd(const float* dlog0, const float* min_disp, cons
 int falnet_med_sweep_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp,
                          const float* t_host, int V, float* views, float* disps, int B, int N, int H, int W, void* stream);
 
+/* Free-viewpoint rendering of the logits of one forward: a homography plane sweep (csrc/med_pose.hip; inference only: no gradient, not
+ * replayable -- falnet_replay_op_index: -1).  Plane n is the plane Z = fx b / s_n of the left camera, s_n = d_n (W-1)/W (the head's and the
+ * sweep's table, built on the device from min_disp / max_disp).  A target camera with centre c (source-camera coordinates), rotation R
+ * (X_t = R (X_s - c)) and intrinsics K_t travels as 12 doubles:
+ *   A = K R^T K_t^-1   (3 x 3, row-major: target pixel -> ray direction in source pixel coordinates)     E = K c / (fx b)   (3)
+ * For target pixel (x, y): q = A (x, y, 1), u0 = q_x / q_z, v0 = q_y / q_z; plane n is sampled at
+ *   u_n = s_n E_x + w_n u0,  v_n = s_n E_y + w_n v0,  w_n = 1 - s_n E_z      iff q_z > 0 and w_n > 0,
+ * bilinearly over four taps that read 0 outside [0, H-1] x [0, W-1] (logits and image alike); a plane that is not sampled, or whose taps all
+ * fall outside, takes part in the softmax with logit 0 (not -inf), as in the head and the sweep.  With P_n the softmax of the warped logits:
+ *   views [B][V][3][H][W] = sum_n P_n bilinear(left_c, u_n, v_n)
+ *   disps [B][V][1][H][W] = sum_n d_n P_n                       (full-baseline pixels of the source planes, as the sweep's disps)
+ *   cover [B][V][1][H][W] = sum_n P_n omega_n   in [0, 1]       (omega_n: the bilinear weights of the taps inside the image, 0 when not sampled)
+ * Any of the three may be NULL, not all; `left` may be NULL when views is.  A = I, E = (t, 0, 0) is falnet_med_sweep_fwd's view t.
+ *   pose_host: HOST array of V records of 12 doubles (A then E), 1 <= V <= 8, passed to the kernel by value.
+ * Coordinates are formed in f64 and clamped as floating values into [-2, W+1] x [-2, H+1] before they become integers; no atomics: two
+ * launches give the same bits.  Returns non-zero, launches nothing and writes nothing on a refused argument: a null required pointer, all
+ * three outputs NULL, V outside 1..8, a non-finite entry of a record, a record whose third row of A is all zero, sizes other than those
+ * falnet_med_head_fwd accepts (and a plane of more than 2^30 pixels: in-plane byte offsets are 32-bit). */
+int falnet_med_pose_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp,
+                        const double* pose_host, int V, float* views, float* disps, float* cover,
+                        int B, int N, int H, int W, void* stream);
+
 /* Per-pixel statistics of the head's distribution over the N planes (csrc/med_stats.hip; inference only: no gradient, not replayable --
  * falnet_replay_op_index: -1).  p_n = softmax_n dlog0, d_n = the head's plane table, a = the FIRST index of the largest stored logit (an exact
  * comparison), win = {n : |n - a| <= 1} within [0, N-1].  `which` selects the outputs by bit; they are written densely as out[B][K][H][W]
