@@ -13,7 +13,8 @@ Two modes:
   * `--synthetic`: seeded image of `--height x --width` (native KITTI 375x1242 by default), timing only -- no dataset on the box.
 The command line is the reference's (Test_KITTI.py:36-60): `-m` is the model NAME and the checkpoint is <-dt>/<-ts>/<-m><-dtl>
 (:119-120; `--checkpoint <file>` names it directly).  Image / PLY dumping (:211-253) is `--dump disp,input,pan,pc,feats` (any subset;
-`--freeview V [--freeview-path orbit|dolly|pan]` adds V free-viewpoint views per frame, fal_net_amd/freeview.py;
+`--freeview V [--freeview-path orbit|dolly|pan]` adds V free-viewpoint views per frame, fal_net_amd/freeview.py, and `--freeview-fill [BETA]`
+their hole-filled versions, fal_net_amd/inpaint.py;
 `--sweep V [--sweep-range LO HI]` adds V views along the baseline and the right view's disparity, fal_net_amd/views.py;
 `--stats KINDS` adds maps of the per-pixel disparity distribution (spread, entropy, arg-max plane, peak mass, peak disparity),
 `--pc-min-conf C` keeps only the confident vertices of the point cloud and `--disparity peak` evaluates the peak disparity, fal_net_amd/confidence.py;
@@ -157,7 +158,21 @@ parser.add_argument('--freeview-path', default='orbit', choices=['orbit', 'dolly
                          'forward from 0 to Z, pan turns on the spot from -DEG to DEG')
 parser.add_argument('--freeview-amp', type=float, nargs=3, default=[0.5, 0.25, 0.5], metavar=('X', 'Y', 'Z'), help='--freeview: amplitudes of the path in baselines')
 parser.add_argument('--freeview-yaw', type=float, default=3.0, metavar='DEG', help='--freeview: yaw amplitude of the path in degrees')
+parser.add_argument('--freeview-fill', type=float, nargs='?', const=4.0, default=None, metavar='BETA',
+                    help='--freeview: also fill the holes of every view from the background (fal_net_amd/inpaint.py: a pull-push pyramid biased towards '
+                         'small disparity by BETA in [0, 8], 4 when the switch is given alone) into Freeview/<frame>_p<pose>_filled.png')
 FREEVIEW_ARGS = ('freeview', 'freeview_path', 'freeview_amp', 'freeview_yaw')
+FREEVIEW_FILL_ARGS = ('freeview_fill',)
+
+
+def check_freeview_fill_args(a):
+    """--freeview-fill belongs to --freeview, and its bias to [0, 8] (fal_net_amd/inpaint.py)."""
+    if a.freeview_fill is None:
+        return
+    if a.freeview is None:
+        raise SystemExit('--freeview-fill fills the holes of the --freeview views: give --freeview V as well')
+    if not 0.0 <= a.freeview_fill <= 8.0:  # a NaN fails both comparisons
+        raise SystemExit('--freeview-fill needs 0 <= BETA <= 8, got {}'.format(a.freeview_fill))
 
 
 def freeview_poses(a):
@@ -370,6 +385,7 @@ def main():
     dtype = {'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[args.dtype]
     post = 'flip' if args.f_post_process else ('ms_pp' if args.ms_post_process else 'none')
     refuse_out_of_scope(args)
+    check_freeview_fill_args(args)
     check_confidence_args(args)
     check_lidar_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
@@ -446,8 +462,12 @@ def main():
         if sweep_writer is not None:
             print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
         if freeview_writer is not None:
-            print(json.dumps({'freeview': dict(freeview_writer.summary(), poses=args.freeview, path=args.freeview_path, amp=list(args.freeview_amp),
-                                               yaw=args.freeview_yaw, camera='nominal')}))
+            fv_line = dict(freeview_writer.summary(), poses=args.freeview, path=args.freeview_path, amp=list(args.freeview_amp), yaw=args.freeview_yaw,
+                           camera='nominal')
+            if args.freeview_fill is not None:
+                from fal_net_amd import inpaint
+                fv_line['fill'] = {'beta': args.freeview_fill, 'floor': inpaint.FLOOR, 'levels': inpaint.levels(args.height, args.width)}
+            print(json.dumps({'freeview': fv_line}))
         if stats_writer is not None:
             print(json.dumps({'stats': stats_writer.summary()}))
 
@@ -472,6 +492,7 @@ def main():
             hidden += () if args.pseudo_lidar else LIDAR_ARGS
             hidden += () if args.sparsification is not None else SPARSIFICATION_ARGS
             hidden += () if args.freeview is not None else FREEVIEW_ARGS
+            hidden += () if args.freeview_fill is not None else FREEVIEW_FILL_ARGS
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         if args.pseudo_lidar:
@@ -484,7 +505,7 @@ def main():
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
                                  disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics,
-                                 freeview_writer=freeview_writer, freeview_poses=fv_poses)
+                                 freeview_writer=freeview_writer, freeview_poses=fv_poses, freeview_fill=args.freeview_fill)
         if args.view_metrics:
             view = res['view']
             write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
@@ -528,7 +549,7 @@ def main():
         if sweep_writer is not None:
             inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
         if freeview_writer is not None:
-            inference.freeview_frame(freeview_writer, 0, pan_model, left, min_disp, max_disp, fv_poses)
+            inference.freeview_frame(freeview_writer, 0, pan_model, left, min_disp, max_disp, fv_poses, fill_beta=args.freeview_fill)
         if stats_writer is not None:
             inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
         if lidar_writer is not None:

@@ -153,6 +153,9 @@ SIGNATURES = {
     "falnet_med_sweep_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_pose_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "falnet_med_stats_fwd": [_P, _P, _P, C.c_uint, _P, _I, _I, _I, _I, _P],
+    "falnet_inpaint_levels": [_I, _I],
+    "falnet_inpaint_workspace_bytes": [_I, _I, _I, _I],
+    "falnet_inpaint_fwd": [_P, _P, _P, _P, _F, _F, _P, _P, _L, _I, _I, _I, _I, _P],
     "falnet_compact_workspace_bytes": [_L],
     "falnet_compact_records": [_P, _I, _P, _F, _L, _P, _P, _P, _P],
     "falnet_l1_fwd": [_P, _P, _P, _I, _I, _L, _F, _P, _I, _P],
@@ -220,7 +223,8 @@ SIGNATURES = {
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
              "falnet_lidar_workspace_bytes": C.c_int64, "falnet_sort_u32_workspace_bytes": C.c_int64,
-             "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64}
+             "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64,
+             "falnet_inpaint_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

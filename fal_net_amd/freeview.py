@@ -10,7 +10,8 @@ the special case "identity rotation, centre on the x axis".
   paths.orbit / paths.dolly / paths.pan          lists of pose() keyword sets for n frames
   warp(dlog0, left, min_disp, max_disp, poses)   the raw wrapper of falnet_med_pose_fwd (launches of at most 8 poses)
   render(model, left, min_disp, max_disp, poses) one no_grad disparity-only forward of the model, then warp over its logits
-  FreeviewWriter(save_path)                      Freeview/{frame:010d}_p{pose:02d}.png and ..._cover.png
+  fill_views(out, max_disp, beta)                the holes of warp()'s views and disparities filled from the background (fal_net_amd/inpaint.py)
+  FreeviewWriter(save_path)                      Freeview/{frame:010d}_p{pose:02d}.png and ..._cover.png (write_filled: ..._filled.png)
 
 Geometry: target camera with centre c (source-camera coordinates), rotation R (X_t = R (X_s - c)) and intrinsics K_t:
     A = K R^T K_t^-1      E = K c / (fx b)
@@ -166,17 +167,51 @@ def warp(dlog0, left, min_disp, max_disp, poses, want=OUTPUTS):
     return out
 
 
-def render(model, left, min_disp, max_disp, poses, want=OUTPUTS):
+FILL_BETA = 4.0  # fill_views' default bias: chosen from the step-scene table of DESIGN.md section 7i (a 16-wide hole comes out 96 % background), not tuned
+
+
+def fill_views(out, max_disp, beta=FILL_BETA, floor=2.0 ** -10):
+    """The holes of warp()'s result filled (fal_net_amd/inpaint.py): `out` needs "view" (B, V, 3, H, W), "cover" and "disp" (B, V, 1, H, W);
+    max_disp: B values in pixels, the guide's scale per sample.  One C = 4 call over all B V images: the colour channels as they are (view is
+    premultiplied by cover already), disp cover as the fourth premultiplied channel, weight = cover, guide = disp: what a hole receives comes
+    from the side of SMALLER disparity, the background.  beta in [0, 8]; the default 4.0 is a choice read off the step-scene table (DESIGN.md
+    section 7i), not a tuned value.  -> {"view": (B, V, 3, H, W), "disp": (B, V, 1, H, W)}, un-premultiplied and fully weighted."""
+    from . import inpaint
+    beta, floor = inpaint.check_params(beta, floor)
+    missing = [k for k in OUTPUTS if k not in out]
+    if missing:
+        raise ValueError("freeview.fill_views: the result of warp() lacks {}".format(missing))
+    view, disp, cover = out["view"], out["disp"], out["cover"]
+    if view.dim() != 5 or view.shape[2] != 3 or tuple(disp.shape) != tuple(view.shape[:2]) + (1,) + tuple(view.shape[3:]) or cover.shape != disp.shape:
+        raise ValueError("freeview.fill_views: expected view (B, V, 3, H, W) with disp and cover (B, V, 1, H, W), got {}, {} and {}".format(
+            tuple(view.shape), tuple(disp.shape), tuple(cover.shape)))
+    B, V = view.shape[:2]
+    if not torch.is_tensor(max_disp) or max_disp.numel() != B:
+        raise ValueError("freeview.fill_views: max_disp must hold one value per sample (B={})".format(B))
+    scale = _f32(max_disp, "max_disp").reshape(B, 1).expand(B, V).contiguous()
+    filled = inpaint.fill(torch.cat([view, disp * cover], 2), cover, guide=disp, guide_scale=scale, beta=beta, floor=floor)
+    return {"view": filled[:, :, :3].contiguous(), "disp": filled[:, :, 3:].contiguous()}
+
+
+def render(model, left, min_disp, max_disp, poses, want=OUTPUTS, fill=None):
     """One no_grad disparity-only forward of `model` (FAL_netA / B / C, any compute dtype: the logits are planar f32 in all of them), then
     warp over the plan's own logits with the plan's prologue-processed min_disp / max_disp, as views.render reaches them.
-    -> (the dict of warp(), the forward's disparity (B, 1, H, W))."""
+    -> (the dict of warp(), the forward's disparity (B, 1, H, W)).  fill=beta adds "view_filled" and "disp_filled" (fill_views with that
+    beta; all three outputs are rendered for it and those not in `want` dropped again); fill=None does exactly what it did before."""
     recs = check_poses(poses)
     want = check_want(want)
+    if fill is not None:
+        from . import inpaint
+        inpaint.check_params(fill, 2.0 ** -10)
     with torch.no_grad():
         disp = model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)
         B, _, H, W = left.shape
         buf = model._plan(B, H, W, left.device).buf  # the plan this forward has just run: its buffers hold the logits until the next forward
-        out = warp(buf["dlog0"], buf["left"], buf["min_disp"], buf["max_disp"], recs, want)
+        out = warp(buf["dlog0"], buf["left"], buf["min_disp"], buf["max_disp"], recs, want if fill is None else OUTPUTS)
+        if fill is not None:
+            filled = fill_views(out, buf["max_disp"], beta=fill)
+            out = {k: out[k] for k in want}
+            out["view_filled"], out["disp_filled"] = filled["view"], filled["disp"]
     return out, disp
 
 
@@ -192,6 +227,7 @@ class FreeviewWriter:
         os.makedirs(self.path, exist_ok=True)
         self.files = 0
         self.frames = 0
+        self.filled = 0
         self._cover_sum = None
         self._cover_n = 0
 
@@ -213,6 +249,19 @@ class FreeviewWriter:
         self._cover_n += cover.numel()
         self.frames += 1
 
+    def write_filled(self, i, filled):
+        """filled (1, V, 3, H, W), the hole-filled views of frame `i` (fill_views): Freeview/{frame:010d}_p{pose:02d}_filled.png."""
+        from PIL import Image
+        from . import dumps
+        rgb = dumps.image_u8(filled[0]).cpu().numpy()         # (V, H, W, 3)
+        for p in range(rgb.shape[0]):
+            Image.fromarray(rgb[p]).save(os.path.join(self.path, "{:010d}_p{:02d}_filled.png".format(i, p)))
+            self.files += 1
+        self.filled += rgb.shape[0]
+
     def summary(self):
-        return {"frames": self.frames, "files": self.files,
-                "mean_cover": float(self._cover_sum) / self._cover_n if self._cover_n else None}
+        out = {"frames": self.frames, "files": self.files,
+               "mean_cover": float(self._cover_sum) / self._cover_n if self._cover_n else None}
+        if self.filled:
+            out["filled"] = self.filled
+        return out

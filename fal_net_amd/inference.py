@@ -74,14 +74,16 @@ def sweep_frame(sweep_writer, i, pan_model, left, min_disp, max_pix, fractions):
     sweep_writer.write(i, imgs[:, :len(fractions)], right_disp=disps[:, ts.index(1.0)])
 
 
-def freeview_frame(freeview_writer, i, pan_model, left, min_disp, max_pix, pose_kwargs):
+def freeview_frame(freeview_writer, i, pan_model, left, min_disp, max_pix, pose_kwargs, fill_beta=None):
     """Frame `i` through a freeview.FreeviewWriter: the views and cover maps of the target cameras `pose_kwargs` (freeview.pose keyword sets, as
     freeview.paths returns them) around the nominal camera of the frame's size, from the logits of one more disparity-only forward
-    (freeview.render)."""
+    (freeview.render).  fill_beta: also the hole-filled views (freeview.fill_views with that bias) as ..._filled.png."""
     from . import freeview as FV
     K = FV.camera(left.shape[-2], left.shape[-1])
-    out, _ = FV.render(pan_model, left, min_disp, max_pix, [FV.pose(K, **kw) for kw in pose_kwargs], want=("view", "cover"))
+    out, _ = FV.render(pan_model, left, min_disp, max_pix, [FV.pose(K, **kw) for kw in pose_kwargs], want=("view", "cover"), fill=fill_beta)
     freeview_writer.write(i, out["view"], out["cover"])
+    if fill_beta is not None:
+        freeview_writer.write_filled(i, out["view_filled"])
 
 
 def stats_frame(stats_writer, i, pan_model, left, disp, min_disp, max_pix):
@@ -142,7 +144,7 @@ def peak_disparity(pan_model, left, min_disp, max_pix):
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
              sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None, sparsification=None, view_metrics=False,
-             freeview_writer=None, freeview_poses=None):
+             freeview_writer=None, freeview_poses=None, freeview_fill=None):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -155,7 +157,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     device_metrics: the depth errors (median scaling included) and the EPE come from the kernels behind fal_net_amd/metrics.py -- no map and no
     metric is copied to the host per frame; the results table is read after the last frame (and on the iterations that print, for the running a1).
     sweep_writer / sweep_fractions: a dumps.SweepWriter and baseline fractions -- every frame's views along the baseline are written too (sweep_frame).
-    freeview_writer / freeview_poses: a freeview.FreeviewWriter and freeview.pose keyword sets -- every frame's free-viewpoint views are written too (freeview_frame).
+    freeview_writer / freeview_poses: a freeview.FreeviewWriter and freeview.pose keyword sets -- every frame's free-viewpoint views are written too (freeview_frame);
+    freeview_fill: a bias beta -- their hole-filled versions as well (freeview.fill_views).
     stats_writer: a confidence.StatsWriter -- every frame's distribution statistics and its confidence-filtered point cloud are written too (stats_frame).
     lidar_writer: a pseudo_lidar.PseudoLidarWriter -- every frame's disparity is also written as a Velodyne-format scan (lidar_frame).
     sparsification: a sparsification.SparsificationTable built with the score names -- every frame with ground truth also leaves its sparsification
@@ -230,7 +233,7 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                 if sweep_writer is not None:
                     sweep_frame(sweep_writer, n, pan_model, left, mn, mx, sweep_fractions)
                 if freeview_writer is not None:
-                    freeview_frame(freeview_writer, n, pan_model, left, mn, mx, freeview_poses)
+                    freeview_frame(freeview_writer, n, pan_model, left, mn, mx, freeview_poses, fill_beta=freeview_fill)
                 if stats_writer is not None:
                     stats_frame(stats_writer, n, pan_model, left, disp, mn, mx)
                 if lidar_writer is not None:

@@ -442,6 +442,37 @@ int falnet_med_pose_fwd(const float* dlog0, const float* left, const float* min_
                         const double* pose_host, int V, float* views, float* disps, float* cover,
                         int B, int N, int H, int W, void* stream);
 
+/* Hole filling of a premultiplied image: background-biased pull-push (csrc/inpaint.hip; inference only: no gradient, not replayable --
+ * falnet_replay_op_index: -1).  Made for falnet_med_pose_fwd's outputs (values = views, a colour premultiplied by its weight; weight = cover;
+ * guide = disps), but any premultiplied image will do.  Per image, all planar f32:
+ *   values [I][C][H][W] premultiplied, 1 <= C <= 4; weight [I][1][H][W] in [0, 1]; guide [I][1][H][W] and guide_scale [I] (device, positive),
+ *   both optional; beta in [0, 8]; floor in (0, 1] (2^-10 is the usual one); out [I][C][H][W]: the un-premultiplied, fully weighted image.
+ * Level 0:  keep = weight >= floor;  w0 = keep ? weight : 0,  c0 = keep ? values : 0  (selects, not multiplies: a NaN under a dropped pixel
+ *   does not leak);  g = exp(-beta guide / guide_scale), g = 1 when beta = 0 (guide is never read then);  the stored triple is
+ *   (cg, wg, a) = (c0 g, w0 g, w0).
+ * Pull, level l -> l + 1, sizes H_{l+1} = (H_l + 1) / 2 and the same for W, until 1 x 1 (L = falnet_inpaint_levels pulls): each coarse cell
+ *   sums its existing fine cells (2 x 2, fewer at odd ends) of all C + 2 channels, then all C + 2 channels are multiplied by 1 / a_sum where
+ *   a_sum > 1, so a <= 1.
+ * Apex:  div(n, d) = d > 0 ? n / d : 0;  F_L = div(cg_L, wg_L),  G_L = div(wg_L, a_L).
+ * Push, level l + 1 -> l.  up() is the 2x tent filter: even fine index i takes coarse taps i/2 - 1 and i/2 with weights 1/4 and 3/4, odd i
+ *   takes (i-1)/2 and (i-1)/2 + 1 with 3/4 and 1/4; taps are clamped into the coarse level; x and y are separable.
+ *   UG = up(G_{l+1}),  U = div(up(F_{l+1} G_{l+1}), UG);
+ *   l >= 1:  F_l = a_l div(cg_l, wg_l) + (1 - a_l) U,   G_l = a_l div(wg_l, a_l) + (1 - a_l) UG;
+ *   l = 0:   out = c0 + (1 - w0) U;        L = 0 (a 1 x 1 image):  out = c0 + (1 - w0) F_0.
+ * The bias towards small `guide` (the background, when guide is a disparity) travels through both directions: in the pull as the factor g of
+ * every sum, in the push as G, the mean g of what a cell holds, which weights the coarse taps.  Pixels with weight == 1 come back bit for bit.
+ * No atomics and every sum in a fixed order: two calls give the same bits and image i of a batch equals its one-image call.
+ *   falnet_inpaint_levels(H, W): L (-1 on a refused size).
+ *   falnet_inpaint_workspace_bytes(C, H, W, images): the caller-provided workspace (levels 1..L of C + 2 channels; the push keeps its
+ *   results in them), -1 on a refused argument; nothing is allocated inside a launch function.  The workspace belongs to one stream at a time.
+ * falnet_inpaint_fwd returns non-zero, launches nothing and writes nothing on a refused argument: a null required pointer (values, weight,
+ * out; the workspace where its size is not 0), guide or guide_scale null with beta > 0, out overlapping values, C outside 1..4, I, H or W below
+ * 1, a plane above 2^30 pixels, beta not in [0, 8] or not finite, floor not in (0, 1], a workspace smaller than reported. */
+int falnet_inpaint_levels(int H, int W);
+int64_t falnet_inpaint_workspace_bytes(int C, int H, int W, int images);
+int falnet_inpaint_fwd(const float* values, const float* weight, const float* guide, const float* guide_scale, float beta, float floor,
+                       float* out, void* workspace, int64_t workspace_bytes, int I, int C, int H, int W, void* stream);
+
 /* Per-pixel statistics of the head's distribution over the N planes (csrc/med_stats.hip; inference only: no gradient, not replayable --
  * falnet_replay_op_index: -1).  p_n = softmax_n dlog0, d_n = the head's plane table, a = the FIRST index of the largest stored logit (an exact
  * comparison), win = {n : |n - a| <= 1} within [0, N-1].  `which` selects the outputs by bit; they are written densely as out[B][K][H][W]
