@@ -19,9 +19,10 @@ import os
 import torch
 
 from . import _lib as L
+from . import med_logits as M
+from .med_logits import MAX_PLANES  # noqa: F401  (part of this module's interface)
 
 KINDS = ("mean", "std", "entropy", "arg", "conf", "peak")  # bit k of `which` is KINDS[k]
-MAX_PLANES = 128  # HEAD_MAXN
 
 
 def which_bits(which):
@@ -37,27 +38,11 @@ def which_bits(which):
     return bits, [k for k in KINDS if k in names]
 
 
-def _f32(x, what):
-    if not x.is_cuda:
-        raise RuntimeError("fal_net_amd.confidence runs on an MI355X only (no CPU fallback); {} is on {}".format(what, x.device))
-    return x.detach().to(torch.float32).contiguous()
-
-
 def stats(dlog0, min_disp, max_disp, which=("std", "conf", "peak")):
     """dlog0 (B, N, H, W) planar f32 logits, min_disp / max_disp: B values in pixels -> {name: (B, 1, H, W) f32} for the names in `which`.
     Every argument is checked before the launch."""
     bits, order = which_bits(which)
-    if dlog0.dim() != 4:
-        raise ValueError("confidence.stats: expected dlog0 (B, N, H, W), got {}".format(tuple(dlog0.shape)))
-    B, N, H, W = dlog0.shape
-    if not 2 <= N <= MAX_PLANES:
-        raise ValueError("confidence.stats: N={} outside [2, {}]".format(N, MAX_PLANES))
-    if min(B, H, W) < 1:
-        raise ValueError("confidence.stats: empty logits {}".format(tuple(dlog0.shape)))
-    if min_disp.numel() != B or max_disp.numel() != B:
-        raise ValueError("confidence.stats: min_disp / max_disp must hold one value per sample (B={})".format(B))
-    dlog0 = _f32(dlog0, "dlog0")
-    mn, mx = _f32(min_disp, "min_disp").reshape(-1), _f32(max_disp, "max_disp").reshape(-1)
+    (dlog0, _, mn, mx), (B, N, H, W) = M.check_logits("confidence.stats", dlog0, min_disp, max_disp)
     out = torch.empty(B, len(order), H, W, dtype=torch.float32, device=dlog0.device)
     L.check(L.lib().falnet_med_stats_fwd(L.ptr(dlog0), L.ptr(mn), L.ptr(mx), bits, L.ptr(out), B, N, H, W, L.stream_ptr()), "med_stats_fwd")
     return {k: out[:, i:i + 1] for i, k in enumerate(order)}
@@ -69,9 +54,7 @@ def from_model(model, left, min_disp, max_disp, which=("std", "conf", "peak")):
     (B, 1, H, W))."""
     which_bits(which)
     with torch.no_grad():
-        disp = model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)
-        B, _, H, W = left.shape
-        buf = model._plan(B, H, W, left.device).buf  # the plan this forward has just run: its buffers hold the logits until the next forward
+        buf, disp = M.forward_logits(model, left, min_disp, max_disp)
         st = stats(buf["dlog0"], buf["min_disp"], buf["max_disp"], which)
     return st, disp
 
@@ -89,7 +72,7 @@ def compact(records, score, threshold, count=None, workspace=None):
             records.shape[0] if records.dim() else 0, rec_bytes, n))
     if not records.is_contiguous():
         raise ValueError("confidence.compact: records must be contiguous")
-    score = _f32(score, "score").reshape(-1)
+    score = M.f32(score, "score", "confidence").reshape(-1)
     lib = L.lib()
     out = torch.empty_like(records)
     count = torch.empty(1, dtype=torch.int64, device=records.device) if count is None else count
@@ -109,7 +92,7 @@ def filter_point_cloud(img, disp, score, threshold, packed=True, focal=None, bas
     B, n = pc.shape[0], disp.shape[-2] * disp.shape[-1]
     if tuple(score.shape) != (B, 1) + tuple(disp.shape[-2:]):
         raise ValueError("confidence.filter_point_cloud: score {} does not match the disparity {}".format(tuple(score.shape), tuple(disp.shape)))
-    score = _f32(score, "score").view(B, n)
+    score = M.f32(score, "score", "confidence").view(B, n)
     counts = torch.empty(B, dtype=torch.int64, device=pc.device)
     ws = torch.empty(max(int(L.lib().falnet_compact_workspace_bytes(n)) // 8, 1), dtype=torch.int64, device=pc.device)
     outs = []

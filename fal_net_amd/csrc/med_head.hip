@@ -8,28 +8,15 @@
 // pixels x and walks the planes with a chunked online softmax (one rescale per 8 planes), so no
 // cross-lane reduction is needed and the only HBM traffic is the N logit rows, read once.
 // HBM-bound: algorithmic bytes (N+7)*HW*4 forward, (2N+7)*HW*4 backward per sample.
-#include <math.h>
-#include "common.h"
+#include "med_planes.h"
 
 #define HEAD_THREADS 256
-#define HEAD_MAXN 128
 #define CH 8  // planes per online-softmax chunk
-
-struct PlaneTab {  // per-sample plane table in LDS
-    float d[HEAD_MAXN];  // disparity of plane n in pixels (FAL_netB.py:223-225)
-    float a[HEAD_MAXN];  // fractional part of the shift s_n = d_n (W-1)/W
-    int k[HEAD_MAXN];    // integer part
-};
 
 __device__ __forceinline__ void build_plane_tab(PlaneTab& t, float mn, float mx, int N, int W) {
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
-        const float c = (float)n / (float)(N - 1);
-        const float d = mx * expf(logf(mx / mn) * (c - 1.0f));
-        const float s = d * (float)(W - 1) / (float)W;  // 2d/W normalised * (W-1)/2 (align_corners=True)
-        const float kf = floorf(s);
-        t.d[n] = d;
-        t.k[n] = (int)kf;
-        t.a[n] = s - kf;
+        t.d[n] = med_plane_disp(mn, mx, n, N);
+        med_split_shift(med_plane_shift(t.d[n], W), t.k[n], t.a[n]);
     }
 }
 
@@ -684,28 +671,50 @@ __global__ __launch_bounds__(HEAD_THREADS) void med_maskr_acfalse_kernel(
 }
 
 // ---------------------------------------------------------------------------------------- C-ABI
-#include <stdlib.h>
-// FALNET_HEAD_V1=1: first forward kernel (per-lane global taps) instead of the LDS-staged one (A/B, tests)
+// A/B switches, each read once: FALNET_HEAD_V1=1 / FALNET_HEAD_BWD_V1=1 take the first forward (per-lane global taps) / NHWC backward kernel
 static const bool g_head_v1 = [] { const char* e = falnet_ab_env("FALNET_HEAD_V1"); return e && e[0] == '1'; }();
+static const bool g_head_bwd_v1 = [] { const char* e = falnet_ab_env("FALNET_HEAD_BWD_V1"); return e && e[0] == '1'; }();
 
-// wave-neighbour kernels (med_head2.hip)
+// second-generation kernels (med_head2.hip): the shapes each takes, and their launches
 bool falnet_head_wave_applicable(int W);
 bool falnet_head_fwd_lds2_applicable(int N, int W);
 bool falnet_head_bwd_lds2_applicable(int N, int W, int dtype);
-bool falnet_head_fwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, float* disp,
+void falnet_head_fwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, float* disp,
                                  float* p_im0, float* stats, int B, int N, int H, int W, hipStream_t stream);
-bool falnet_head_bwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* disp,
+void falnet_head_bwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* disp,
                                  const float* p_im0, const float* stats, const float* gdisp, const float* gpan, void* gdlog0, int cpad,
                                  int dtype, int B, int N, int H, int W, hipStream_t stream);
 void falnet_head_bwd_wave_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* disp,
-                               const float* p_im0, const float* stats, const float* gdisp, const float* gpan, void* gdlog0, int cpad,
-                               int dtype, int B, int N, int H, int W, hipStream_t stream);
+                                 const float* p_im0, const float* stats, const float* gdisp, const float* gpan, void* gdlog0, int cpad,
+                                 int dtype, int B, int N, int H, int W, hipStream_t stream);
 
-static int check_head(int B, int N, int H, int W) {
-    FALNET_CHECK_ARG(B > 0 && H > 0 && W > 0, "med_head: empty shape B=%d H=%d W=%d", B, H, W);
-    FALNET_CHECK_ARG(N >= 2 && N <= HEAD_MAXN, "med_head: N=%d outside [2,%d]", N, HEAD_MAXN);
-    FALNET_CHECK_ARG((size_t)(W + 3) * 5 * 4 + sizeof(PlaneTab) <= 160 * 1024, "med_head: W=%d too wide for LDS", W);
-    return 0;
+static int check_head(int B, int N, int H, int W) { return med_check_shape("med_head", " for LDS", B, N, H, W); }
+
+// The ten head kernels and the one place that says which a shape takes: the entry points launch, and falnet_med_head_kernel_name reports, what choose_* returns
+enum HeadKernel { HK_FWD, HK_FWD_LDS, HK_FWD_LDS2, HK_FWD_LDS2_512, HK_BWD_PLANAR, HK_BWD_NHWC, HK_BWD_LDS, HK_BWD_LDS2, HK_BWD_LDS2_512, HK_BWD_WAVE };
+static const char* const HEAD_KERNEL_NAMES[] = {
+    "med_head_fwd_kernel", "med_head_fwd_lds_kernel", "med_head_fwd_lds2_kernel", "med_head_fwd_lds2_kernel<512 threads>",
+    "med_head_bwd_kernel<planar>", "med_head_bwd_kernel<nhwc>", "med_head_bwd_lds_kernel", "med_head_bwd_lds2_kernel",
+    "med_head_bwd_lds2_kernel<512 threads>", "med_head_bwd_wave_kernel"};
+
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static size_t head_fwd_lds_bytes(int W) { return sizeof(PlaneTab) + (3 + CH) * (size_t)((W + 7) & ~3) * sizeof(float); }
+
+// falnet_med_head_fwd.  aligned: dlog0 and left on 16 bytes.
+static HeadKernel choose_head_fwd(int N, int W, bool aligned) {
+    if (g_head_v1) return HK_FWD;
+    if (aligned && falnet_head_fwd_lds2_applicable(N, W)) return W > 1024 ? HK_FWD_LDS2_512 : HK_FWD_LDS2;
+    if ((W + HEAD_THREADS - 1) / HEAD_THREADS <= 8 && head_fwd_lds_bytes(W) <= 64 * 1024) return HK_FWD_LDS;
+    return HK_FWD;
+}
+
+// falnet_med_head_bwd_nhwc.  io_aligned: dlog0 and the gradient on 16 bytes; all_aligned: every operand.
+static HeadKernel choose_head_bwd_nhwc(int N, int W, int dtype, bool io_aligned, bool all_aligned) {
+    if (g_head_bwd_v1) return HK_BWD_NHWC;
+    if (io_aligned && falnet_head_bwd_lds2_applicable(N, W, dtype)) return W > 1024 ? HK_BWD_LDS2_512 : HK_BWD_LDS2;
+    if (W > 1024 && falnet_head_wave_applicable(W) && all_aligned) return HK_BWD_WAVE;
+    if (W <= 4 * HEAD_THREADS) return HK_BWD_LDS;
+    return HK_BWD_NHWC;
 }
 
 extern "C" int falnet_med_head_fwd(const float* dlog0, const float* left, const float* min_disp,
@@ -715,33 +724,32 @@ extern "C" int falnet_med_head_fwd(const float* dlog0, const float* left, const 
     if (int r = check_head(B, N, H, W)) return r;
     FALNET_CHECK_ARG(dlog0 && min_disp && max_disp, "med_head_fwd: null input");
     FALNET_CHECK_ARG(!p_im0 || left, "med_head_fwd: p_im0 requested without left image");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!g_head_v1 && al16(dlog0) && al16(left) &&
-        falnet_head_fwd_lds2_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, B, N, H, W, (hipStream_t)stream))
-        FALNET_RETURN_LAUNCH();
-    const int ppt = (W + HEAD_THREADS - 1) / HEAD_THREADS;
-    const size_t WP = (size_t)((W + 7) & ~3);
-    const size_t lds2 = sizeof(PlaneTab) + (3 + CH) * WP * sizeof(float);
-    if (ppt <= 8 && lds2 <= 64 * 1024 && !g_head_v1) {
+    switch (choose_head_fwd(N, W, al16(dlog0) && al16(left))) {
+        case HK_FWD_LDS2: case HK_FWD_LDS2_512:
+            falnet_head_fwd_lds2_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, B, N, H, W, (hipStream_t)stream);
+            break;
+        case HK_FWD_LDS: {
+            const size_t lds2 = head_fwd_lds_bytes(W);
 #define LAUNCH_HEAD(P)                                                                                                   \
     hipLaunchKernelGGL(med_head_fwd_lds_kernel<P>, dim3(B * H), dim3(HEAD_THREADS), lds2, (hipStream_t)stream, dlog0, left, \
                        min_disp, max_disp, disp, p_im0, stats, N, H, W)
-        switch (ppt) {
-            case 1: LAUNCH_HEAD(1); break;
-            case 2: LAUNCH_HEAD(2); break;
-            case 3: LAUNCH_HEAD(3); break;
-            case 4: LAUNCH_HEAD(4); break;
-            case 5: LAUNCH_HEAD(5); break;
-            case 6: LAUNCH_HEAD(6); break;
-            case 7: LAUNCH_HEAD(7); break;
-            default: LAUNCH_HEAD(8); break;
-        }
+            switch ((W + HEAD_THREADS - 1) / HEAD_THREADS) {
+                case 1: LAUNCH_HEAD(1); break;
+                case 2: LAUNCH_HEAD(2); break;
+                case 3: LAUNCH_HEAD(3); break;
+                case 4: LAUNCH_HEAD(4); break;
+                case 5: LAUNCH_HEAD(5); break;
+                case 6: LAUNCH_HEAD(6); break;
+                case 7: LAUNCH_HEAD(7); break;
+                default: LAUNCH_HEAD(8); break;
+            }
 #undef LAUNCH_HEAD
-        FALNET_RETURN_LAUNCH();
+            break;
+        }
+        default:
+            hipLaunchKernelGGL(med_head_fwd_kernel, dim3(B * H), dim3(HEAD_THREADS), sizeof(PlaneTab) + (size_t)3 * (W + 2) * sizeof(float),
+                               (hipStream_t)stream, dlog0, left, min_disp, max_disp, disp, p_im0, stats, N, H, W);
     }
-    const size_t lds = sizeof(PlaneTab) + (size_t)3 * (W + 2) * sizeof(float);
-    hipLaunchKernelGGL(med_head_fwd_kernel, dim3(B * H), dim3(HEAD_THREADS), lds, (hipStream_t)stream, dlog0, left,
-                       min_disp, max_disp, disp, p_im0, stats, N, H, W);
     FALNET_RETURN_LAUNCH();
 }
 
@@ -772,60 +780,46 @@ extern "C" int falnet_med_head_bwd_nhwc(const float* dlog0, const float* left, c
     FALNET_CHECK_ARG(cpad >= N && cpad % 8 == 0, "med_head_bwd_nhwc: cpad=%d must be a multiple of 8 >= N", cpad);
     FALNET_CHECK_ARG(dtype == FALNET_F32 || dtype == FALNET_BF16 || dtype == FALNET_F16, "med_head_bwd_nhwc: bad dtype %d", dtype);
     const size_t lds = sizeof(PlaneTab) + (size_t)5 * (W + 3) * sizeof(float);
-    static const bool v1 = [] { const char* e = falnet_ab_env("FALNET_HEAD_BWD_V1"); return e && e[0] == '1'; }();
     static const int pair = [] { const char* e = falnet_ab_env("FALNET_HEAD_PAIR"); return (e && e[0] == '0') ? 0 : 1; }();
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!v1 && al16(dlog0) && al16(grad_dlog0_nhwc) &&
-        falnet_head_bwd_lds2_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, grad_dlog0_nhwc, cpad, dtype, B, N, H,
-                                    W, (hipStream_t)stream))
-        FALNET_RETURN_LAUNCH();
-    if (!v1 && W > 1024 && falnet_head_wave_applicable(W) && al16(dlog0) && al16(left) && al16(disp) && al16(p_im0) && al16(stats) && al16(grad_disp) &&
-        al16(grad_p_im0) && al16(grad_dlog0_nhwc)) {
-        falnet_head_bwd_wave_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, grad_dlog0_nhwc, cpad, dtype, B, N,
-                                  H, W, (hipStream_t)stream);
-        FALNET_RETURN_LAUNCH();
-    }
-    if (!v1 && W <= 4 * HEAD_THREADS) {  // LDS-staged plane rows
-        const size_t lds2 = (lds + 15) / 16 * 16 + (size_t)CH * ((W + 11) & ~3) * sizeof(float);
+    const bool io_aligned = al16(dlog0) && al16(grad_dlog0_nhwc);
+    const bool all_aligned = io_aligned && al16(left) && al16(disp) && al16(p_im0) && al16(stats) && al16(grad_disp) && al16(grad_p_im0);
+    switch (choose_head_bwd_nhwc(N, W, dtype, io_aligned, all_aligned)) {
+        case HK_BWD_LDS2: case HK_BWD_LDS2_512:
+            falnet_head_bwd_lds2_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, grad_dlog0_nhwc, cpad, dtype, B,
+                                        N, H, W, (hipStream_t)stream);
+            break;
+        case HK_BWD_WAVE:
+            falnet_head_bwd_wave_launch(dlog0, left, min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, grad_dlog0_nhwc, cpad, dtype, B,
+                                        N, H, W, (hipStream_t)stream);
+            break;
+        case HK_BWD_LDS: {  // LDS-staged plane rows
+            const size_t lds2 = (lds + 15) / 16 * 16 + (size_t)CH * ((W + 11) & ~3) * sizeof(float);
 #define LAUNCH_BWD_LDS(T, P)                                                                                                   \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(med_head_bwd_lds_kernel<T, P>), dim3(B * H), dim3(HEAD_THREADS), lds2, (hipStream_t)stream, dlog0, left, \
                        min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, (T*)grad_dlog0_nhwc, N, H, W, cpad, pair)
-        const int ppt = (W + HEAD_THREADS - 1) / HEAD_THREADS;
+            const int ppt = (W + HEAD_THREADS - 1) / HEAD_THREADS;
 #define BWD_LDS_T(T) if (ppt <= 1) LAUNCH_BWD_LDS(T, 1); else if (ppt == 2) LAUNCH_BWD_LDS(T, 2); else LAUNCH_BWD_LDS(T, 4)
-        FALNET_DISPATCH_DTYPE(dtype, BWD_LDS_T);
+            FALNET_DISPATCH_DTYPE(dtype, BWD_LDS_T);
 #undef BWD_LDS_T
 #undef LAUNCH_BWD_LDS
-        FALNET_RETURN_LAUNCH();
-    }
+            break;
+        }
+        default:
 #define BWD_V1_T(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(med_head_bwd_kernel<T, true>), dim3(B * H), dim3(HEAD_THREADS), lds, (hipStream_t)stream, dlog0, left, \
                                        min_disp, max_disp, disp, p_im0, stats, grad_disp, grad_p_im0, (T*)grad_dlog0_nhwc, N, H, W, cpad)
-    FALNET_DISPATCH_DTYPE(dtype, BWD_V1_T);
+            FALNET_DISPATCH_DTYPE(dtype, BWD_V1_T);
 #undef BWD_V1_T
+    }
     FALNET_RETURN_LAUNCH();
 }
 
-// Which kernel the three entry points above dispatch to for a shape (16-byte aligned operands assumed: torch allocations are) -- the same
-// predicates in the same order.  pass: 0 = falnet_med_head_fwd, 1 = falnet_med_head_bwd (planar f32), 2 = falnet_med_head_bwd_nhwc.
+// Which kernel the three entry points above launch for a shape (16-byte aligned operands assumed: torch allocations are).
+// pass: 0 = falnet_med_head_fwd, 1 = falnet_med_head_bwd (planar f32, one kernel), 2 = falnet_med_head_bwd_nhwc.
 extern "C" int falnet_med_head_kernel_name(int pass, int dtype, int N, int W, char* buf, int len) {
     if (int r = check_head(1, N, 1, W)) return r;
     FALNET_CHECK_ARG(buf && len > 0 && pass >= 0 && pass <= 2, "med_head_kernel_name: bad argument");
-    const char* name;
-    if (pass == 0) {
-        const int ppt = (W + HEAD_THREADS - 1) / HEAD_THREADS;
-        const size_t lds2 = sizeof(PlaneTab) + (3 + CH) * (size_t)((W + 7) & ~3) * sizeof(float);
-        name = (!g_head_v1 && falnet_head_fwd_lds2_applicable(N, W)) ? (W > 1024 ? "med_head_fwd_lds2_kernel<512 threads>" : "med_head_fwd_lds2_kernel")
-               : (!g_head_v1 && ppt <= 8 && lds2 <= 64 * 1024)     ? "med_head_fwd_lds_kernel"
-                                                                    : "med_head_fwd_kernel";
-    } else if (pass == 1) {
-        name = "med_head_bwd_kernel<planar>";
-    } else {
-        static const bool v1 = [] { const char* e = falnet_ab_env("FALNET_HEAD_BWD_V1"); return e && e[0] == '1'; }();
-        name = (!v1 && falnet_head_bwd_lds2_applicable(N, W, dtype)) ? (W > 1024 ? "med_head_bwd_lds2_kernel<512 threads>" : "med_head_bwd_lds2_kernel")
-               : (!v1 && W > 1024 && falnet_head_wave_applicable(W)) ? "med_head_bwd_wave_kernel"
-               : (!v1 && W <= 4 * HEAD_THREADS)                      ? "med_head_bwd_lds_kernel"
-                                                                      : "med_head_bwd_kernel<nhwc>";
-    }
-    snprintf(buf, (size_t)len, "%s", name);
+    const HeadKernel k = pass == 0 ? choose_head_fwd(N, W, true) : pass == 1 ? HK_BWD_PLANAR : choose_head_bwd_nhwc(N, W, dtype, true, true);
+    snprintf(buf, (size_t)len, "%s", HEAD_KERNEL_NAMES[k]);
     return 0;
 }
 

@@ -21,17 +21,13 @@
 //      At 256x512 this form measured SLOWER than (1) (142 / 176 us: it needs 9 waves per row and the kernels are latency-, not
 //      LDS-bound there), at 2x384x1280 162 -> 133 us forward and 306 -> 151 us backward against the first kernels.
 //      (Also measured and dropped: four ADJACENT pixels per thread sharing taps -- stride-4 scalar LDS reads are 4-way bank conflicts.)
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <math.h>
-
-#include "common.h"
+#include "med_planes.h"
 
 bool falnet_head_wave_applicable(int W);
 #define HW_MAXT 1024  // one wave per unit of 62 / 63 output columns: 64 * ceil(units / R) threads, R rounds only for rows wider than 16 units
 #define HW_CH 8  // plane rows staged per chunk = planes per online-softmax rescale = channels per gradient store
 
+static_assert(MED_MAXN == 128, "the register plane table is two planes per lane of a wave");
 struct WavePlanes {  // plane n <-> lane n & 63 of register n >> 6
     float d[2], a[2];
     int k[2];
@@ -42,14 +38,8 @@ __device__ __forceinline__ WavePlanes wave_build_planes(float mn, float mx, int 
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int n = lane + 64 * h;
-        const float c = (float)n / (float)(N - 1);
-        const float d = mx * expf(logf(mx / mn) * (c - 1.0f));  // FAL_netB.py:223-225
-        const float s = d * (float)(W - 1) / (float)W;           // 2d/W normalised * (W-1)/2 (align_corners=True)
-        const float kf = floorf(s);
-        t.d[h] = d;
-        t.k[h] = (int)kf;
-        t.a[h] = s - kf;
+        t.d[h] = med_plane_disp(mn, mx, lane + 64 * h, N);
+        med_split_shift(med_plane_shift(t.d[h], W), t.k[h], t.a[h]);
     }
     return t;
 }
@@ -403,19 +393,18 @@ __global__ __launch_bounds__(NT) void med_head_fwd_lds2_kernel(
 
 bool falnet_head_fwd_lds2_applicable(int N, int W) {
     static const bool off = [] { const char* e = falnet_ab_env("FALNET_HEAD_FWD2"); return e && e[0] == '0'; }();
-    return !(off || (W & 3) || W < 4 || W > 2048 || N + HW_CH > 128);  // (plane table: 128 entries, read up to N - 1 + HW_CH - 1)
+    return !(off || (W & 3) || W < 4 || W > 2048 || N + HW_CH > MED_MAXN);  // (plane table: MED_MAXN entries, read up to N - 1 + HW_CH - 1)
 }
 
-bool falnet_head_fwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, float* disp,
+void falnet_head_fwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, float* disp,
                                  float* p_im0, float* stats, int B, int N, int H, int W, hipStream_t stream) {
-    if (!falnet_head_fwd_lds2_applicable(N, W)) return false;
     const int wp = (W + 7) & ~3;
     const size_t lds = (size_t)(3 + HW_CH) * wp * sizeof(float);
 #define HW_L(P, C, NT) hipLaunchKernelGGL(HIP_KERNEL_NAME(med_head_fwd_lds2_kernel<P, C, NT>), dim3(B * H), dim3(NT), lds, stream, dlog0, left, min_disp, max_disp, disp, p_im0, stats, N, H, W)
     if (W > 1024) {  // 512 threads: the 384 x 1280 shape (3 pixels per thread)
         const int ppt = (W + 511) / 512;
         if (ppt <= 3) HW_L(3, 0, 512); else HW_L(4, 0, 512);
-        return true;
+        return;
     }
     const int ppt = (W + 255) / 256;
     if (W == 512) HW_L(2, 516, 256);
@@ -424,7 +413,6 @@ bool falnet_head_fwd_lds2_launch(const float* dlog0, const float* left, const fl
     else if (ppt == 3) HW_L(3, 0, 256);
     else HW_L(4, 0, 256);
 #undef HW_L
-    return true;
 }
 
 // ---------------------------------------------------------------------------------------- backward, strided form (W <= 1024)
@@ -611,23 +599,21 @@ static void bwd_lds2_launch_t(const float* dlog0, const float* left, const float
 
 bool falnet_head_bwd_lds2_applicable(int N, int W, int dtype) {
     static const bool off = [] { const char* e = falnet_ab_env("FALNET_HEAD_BWD2"); return e && e[0] == '0'; }();
-    if (off || (W & 3) || W < 4 || W > 2048 || N + HW_CH > 128) return false;
+    if (off || (W & 3) || W < 4 || W > 2048 || N + HW_CH > MED_MAXN) return false;
     // 8 x 384 x 1280, N = 96: 16-bit gradient 991 us here vs 955 us on the wave-neighbour kernel (f32: 1277 vs 1357)
     if (W > 1024 && dtype != FALNET_F32 && falnet_head_wave_applicable(W)) return false;
     return true;
 }
 
-bool falnet_head_bwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* disp,
+void falnet_head_bwd_lds2_launch(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* disp,
                                  const float* p_im0, const float* stats, const float* gdisp, const float* gpan, void* gdlog0, int cpad,
                                  int dtype, int B, int N, int H, int W, hipStream_t stream) {
-    if (!falnet_head_bwd_lds2_applicable(N, W, dtype)) return false;
 #define HW_D(T) bwd_lds2_launch_t<T>(dlog0, left, min_disp, max_disp, disp, p_im0, stats, gdisp, gpan, (T*)gdlog0, cpad, B, N, H, W, stream)
     FALNET_DISPATCH_DTYPE(dtype, HW_D);
 #undef HW_D
-    return true;
 }
 
-// ---------------------------------------------------------------------------------------- launch helpers (called from med_head.hip's C-ABI)
+// ---------------------------------------------------------------------------------------- wave-neighbour launch (med_head.hip's C-ABI chooses it)
 bool falnet_head_wave_applicable(int W) {
     static const bool off = [] { const char* e = falnet_ab_env("FALNET_HEAD_WAVE"); return e && e[0] == '0'; }();
     return !off && (W & 3) == 0 && W >= 64 && W <= 62 * 16 * 2;

@@ -1,7 +1,7 @@
 // Free-viewpoint rendering of the MED head's logits: a homography plane sweep (inference only; no backward, not replayable).
 //
 // The logits of one forward are a multiplane image: plane n is the fronto-parallel plane Z = fx b / s_n of the left camera, s_n = d_n (W-1)/W
-// (build_plane_tab's table).  A target camera travels as 12 doubles (include/falnet_hip.h):
+// (the head's table, med_planes.h).  A target camera travels as 12 doubles (include/falnet_hip.h):
 //   A = K R^T K_t^-1   (3 x 3, row-major: target pixel -> ray direction in source pixel coordinates)      E = K c / (fx b)
 // For target pixel (x, y):  q = A (x, y, 1),  u0 = q_x / q_z,  v0 = q_y / q_z;  for plane n
 //   w_n = 1 - s_n E_z      u_n = s_n E_x + w_n u0      v_n = s_n E_y + w_n v0          sampled iff q_z > 0 and w_n > 0
@@ -21,13 +21,11 @@
 // weights and blends are f32.
 // No atomics: two launches give the same bits.
 #include <limits.h>
-#include <math.h>
-#include "common.h"
+#include "med_planes.h"
 
 #define PO_TX 32
 #define PO_TY 8
 #define PO_THREADS (PO_TX * PO_TY)
-#define PO_MAXN 128  // = HEAD_MAXN of med_head.hip
 #define PO_MAXV 8
 #define PO_CH 4      // planes per online-softmax chunk
 
@@ -56,8 +54,8 @@ __global__ __launch_bounds__(PO_THREADS) void med_pose_kernel(
     const float* __restrict__ dlog0, const float* __restrict__ left, const float* __restrict__ min_disp,
     const float* __restrict__ max_disp, const PoseT poses, int V, float* __restrict__ views, float* __restrict__ disps,
     float* __restrict__ cover, int N, int H, int W, int tiles_x, int tiles) {
-    __shared__ double tsx[PO_MAXN], tsy[PO_MAXN], tw[PO_MAXN];  // s_n E_x, s_n E_y, 1 - s_n E_z of this workgroup's view
-    __shared__ float td[PO_MAXN];
+    __shared__ double tsx[MED_MAXN], tsy[MED_MAXN], tw[MED_MAXN];  // s_n E_x, s_n E_y, 1 - s_n E_z of this workgroup's view
+    __shared__ float td[MED_MAXN];
     const int tile = blockIdx.x % tiles, bv = blockIdx.x / tiles;
     const int v = bv % V, b = bv / V;
     const double* rec = poses.r[v];
@@ -65,10 +63,9 @@ __global__ __launch_bounds__(PO_THREADS) void med_pose_kernel(
         const float mn = min_disp[b], mx = max_disp[b];
         const double ex = rec[9], ey = rec[10], ez = rec[11];
         for (int n = threadIdx.x; n < N; n += PO_THREADS) {
-            // build_plane_tab's lines (med_head.hip): at pure-baseline poses the shifts are the sweep's
-            const float c = (float)n / (float)(N - 1);
-            const float d = mx * expf(logf(mx / mn) * (c - 1.0f));
-            const float s = d * (float)(W - 1) / (float)W;
+            // the head's d and s (med_planes.h): at pure-baseline poses the shifts are the sweep's
+            const float d = med_plane_disp(mn, mx, n, N);
+            const float s = med_plane_shift(d, W);
             td[n] = d;
             tsx[n] = (double)s * ex;
             tsy[n] = (double)s * ey;
@@ -199,10 +196,7 @@ __global__ __launch_bounds__(PO_THREADS) void med_pose_kernel(
 extern "C" int falnet_med_pose_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const double* pose_host, int V,
                                    float* views, float* disps, float* cover, int B, int N, int H, int W, void* stream) {
     FALNET_ENTER(stream);
-    // the sizes falnet_med_head_fwd accepts (check_head, med_head.hip)
-    FALNET_CHECK_ARG(B > 0 && H > 0 && W > 0, "med_pose_fwd: empty shape B=%d H=%d W=%d", B, H, W);
-    FALNET_CHECK_ARG(N >= 2 && N <= PO_MAXN, "med_pose_fwd: N=%d outside [2,%d]", N, PO_MAXN);
-    FALNET_CHECK_ARG((size_t)(W + 3) * 5 * 4 + (size_t)PO_MAXN * 12 <= 160 * 1024, "med_pose_fwd: W=%d too wide", W);
+    if (int r = med_check_shape("med_pose_fwd", "", B, N, H, W)) return r;
     FALNET_CHECK_ARG((int64_t)(H + 2) * W + 2 <= (1ll << 30), "med_pose_fwd: H=%d W=%d: a plane of more than 2^30 pixels", H, W);
     FALNET_CHECK_ARG(V >= 1 && V <= PO_MAXV, "med_pose_fwd: V=%d outside [1,%d]", V, PO_MAXV);
     FALNET_CHECK_ARG(views || disps || cover, "med_pose_fwd: no output requested");

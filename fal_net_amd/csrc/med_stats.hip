@@ -1,6 +1,6 @@
 // Per-pixel statistics of the MED head's distribution over the N disparity planes (inference only; no backward, not replayable).
 //
-//   p_n = softmax_n dlog0_n        d_n = the head's plane table (build_plane_tab, med_head.hip)
+//   p_n = softmax_n dlog0_n        d_n = the head's plane table (med_plane_disp, med_planes.h)
 //   a   = FIRST index of the largest stored logit (an exact comparison)        win = {n : |n - a| <= 1} within [0, N-1]
 //   mean    mu = sum p_n d_n                      (falnet_med_head_fwd's disp)
 //   std     sqrt(sum p_n (d_n - mu)^2)            from the CENTRED sum, a second pass over the pixel's planes in registers
@@ -13,11 +13,9 @@
 // constant); a workgroup owns 256 consecutive pixels of one sample's H W plane, so every plane is one coalesced 1 KiB read per workgroup and
 // all N reads of a thread are independent and in flight together.  Each logit is fetched once; the passes after it (maximum and arg-max,
 // sums, centred sum) run on registers.  No cross-lane step, no atomics: a launch repeats bit for bit.
-#include <math.h>
-#include "common.h"
+#include "med_planes.h"
 
 #define ST_THREADS 256
-#define ST_MAXN 128  // = HEAD_MAXN of med_head.hip
 #define ST_NOUT 6
 
 template <int NP>
@@ -28,10 +26,7 @@ __global__ __launch_bounds__(ST_THREADS) void med_stats_kernel(const float* __re
     const int b = blockIdx.x / nblk, cb = blockIdx.x % nblk;
     {
         const float mn = min_disp[b], mx = max_disp[b];
-        for (int n = threadIdx.x; n < N; n += ST_THREADS) {  // build_plane_tab's d, operation by operation
-            const float c = (float)n / (float)(N - 1);
-            td[n] = mx * expf(logf(mx / mn) * (c - 1.0f));
-        }
+        for (int n = threadIdx.x; n < N; n += ST_THREADS) td[n] = med_plane_disp(mn, mx, n, N);  // the head's d
     }
     __syncthreads();
     const int64_t pix = (int64_t)cb * ST_THREADS + threadIdx.x;
@@ -92,10 +87,7 @@ __global__ __launch_bounds__(ST_THREADS) void med_stats_kernel(const float* __re
 extern "C" int falnet_med_stats_fwd(const float* dlog0, const float* min_disp, const float* max_disp, unsigned which, float* out, int B, int N,
                                     int H, int W, void* stream) {
     FALNET_ENTER(stream);
-    // the sizes falnet_med_head_fwd accepts (check_head, med_head.hip)
-    FALNET_CHECK_ARG(B > 0 && H > 0 && W > 0, "med_stats_fwd: empty shape B=%d H=%d W=%d", B, H, W);
-    FALNET_CHECK_ARG(N >= 2 && N <= ST_MAXN, "med_stats_fwd: N=%d outside [2,%d]", N, ST_MAXN);
-    FALNET_CHECK_ARG((size_t)(W + 3) * 5 * 4 + (size_t)ST_MAXN * 12 <= 160 * 1024, "med_stats_fwd: W=%d too wide", W);
+    if (int r = med_check_shape("med_stats_fwd", "", B, N, H, W)) return r;
     FALNET_CHECK_ARG(which != 0 && which < (1u << ST_NOUT), "med_stats_fwd: which=0x%x selects no output or one above bit %d", which, ST_NOUT - 1);
     FALNET_CHECK_ARG(dlog0 && min_disp && max_disp && out, "med_stats_fwd: null pointer");
     const int64_t HW = (int64_t)H * W;
@@ -107,7 +99,7 @@ extern "C" int falnet_med_stats_fwd(const float* dlog0, const float* min_disp, c
     hipLaunchKernelGGL(med_stats_kernel<NP>, grid, dim3(ST_THREADS), 0, (hipStream_t)stream, dlog0, min_disp, max_disp, which, K, out, N, HW, (int)nblk)
     if (N <= 8) STATS_LAUNCH(8);
     else if (N <= 64) STATS_LAUNCH(64);
-    else STATS_LAUNCH(128);
+    else STATS_LAUNCH(MED_MAXN);
 #undef STATS_LAUNCH
     FALNET_RETURN_LAUNCH();
 }

@@ -13,11 +13,9 @@
 // window of the row its taps can reach: [x0 + min k - 2, x0 + 511 + max k + 1] over the launch's views and planes.  Rows wider than 512 are
 // covered by several workgroups whose windows overlap; the overlap is re-read from L2.
 #include <limits.h>
-#include <math.h>
-#include "common.h"
+#include "med_planes.h"
 
 #define SW_THREADS 512
-#define SW_MAXN 128  // = HEAD_MAXN of med_head.hip
 #define SW_MAXV 8
 #define SW_CH 8      // planes per online-softmax chunk, as the head
 #define SW_FB_THREADS 256
@@ -26,14 +24,12 @@ struct SweepT {  // the baseline fractions, by value in the kernel arguments
     float t[SW_MAXV];
 };
 
-// plane n of view t: disparity d (pixels), shift t * d (W-1)/W split into k = floor and a.  The first three lines are build_plane_tab's
-// (med_head.hip), so that t = 1 gives its table bit for bit.  k is clamped as a FLOAT before the conversion: max_disp comes from device
+// plane n of view t: disparity d (pixels), shift t * d (W-1)/W split into k = floor and a.  d and the full shift are the head's own
+// (med_planes.h), so that t = 1 gives its table bit for bit.  k is clamped as a FLOAT before the conversion: max_disp comes from device
 // memory and is not bounded by the entry point; |k| <= W + 2 already puts both taps of every pixel outside the row.
 __device__ __forceinline__ void sweep_plane(float mn, float mx, float t, int n, int N, int W, float& d, int& k, float& a) {
-    const float c = (float)n / (float)(N - 1);
-    d = mx * expf(logf(mx / mn) * (c - 1.0f));
-    const float s = d * (float)(W - 1) / (float)W;
-    const float st = t * s;
+    d = med_plane_disp(mn, mx, n, N);
+    const float st = t * med_plane_shift(d, W);
     const float kf = floorf(st);
     a = st - kf;
     k = (int)fminf(fmaxf(kf, -(float)(W + 2)), (float)(W + 2));
@@ -214,8 +210,8 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(PF <
 __global__ __launch_bounds__(SW_FB_THREADS) void med_sweep_kernel(
     const float* __restrict__ dlog0, const float* __restrict__ left, const float* __restrict__ min_disp,
     const float* __restrict__ max_disp, const SweepT ts, int V, float* __restrict__ views, float* __restrict__ disps, int N, int H, int W) {
-    __shared__ int tk[SW_MAXN];
-    __shared__ float ta[SW_MAXN], td[SW_MAXN];
+    __shared__ int tk[MED_MAXN];
+    __shared__ float ta[MED_MAXN], td[MED_MAXN];
     const int b = blockIdx.x / H, y = blockIdx.x % H, v = blockIdx.y;
     const int64_t HW = (int64_t)H * W;
     const float t = sweep_t(ts, v);
@@ -303,10 +299,7 @@ static int sweep_launch(const float* dlog0, const float* left, const float* min_
 extern "C" int falnet_med_sweep_fwd(const float* dlog0, const float* left, const float* min_disp, const float* max_disp, const float* t_host, int V,
                                     float* views, float* disps, int B, int N, int H, int W, void* stream) {
     FALNET_ENTER(stream);
-    // the sizes falnet_med_head_fwd accepts (check_head, med_head.hip)
-    FALNET_CHECK_ARG(B > 0 && H > 0 && W > 0, "med_sweep_fwd: empty shape B=%d H=%d W=%d", B, H, W);
-    FALNET_CHECK_ARG(N >= 2 && N <= SW_MAXN, "med_sweep_fwd: N=%d outside [2,%d]", N, SW_MAXN);
-    FALNET_CHECK_ARG((size_t)(W + 3) * 5 * 4 + (size_t)SW_MAXN * 12 <= 160 * 1024, "med_sweep_fwd: W=%d too wide", W);
+    if (int r = med_check_shape("med_sweep_fwd", "", B, N, H, W)) return r;
     FALNET_CHECK_ARG((int64_t)B * H * ((W + SW_THREADS - 1) / SW_THREADS) < (1ll << 31), "med_sweep_fwd: B=%d H=%d W=%d: too many rows for one launch", B, H, W);
     FALNET_CHECK_ARG(V >= 1 && V <= SW_MAXV, "med_sweep_fwd: V=%d outside [1,%d]", V, SW_MAXV);
     FALNET_CHECK_ARG(views || disps, "med_sweep_fwd: no output requested");

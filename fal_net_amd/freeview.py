@@ -29,9 +29,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import med_logits as M
+from .med_logits import MAX_PLANES  # noqa: F401  (part of this module's interface)
 
 MAX_POSES = 8      # poses per launch (PO_MAXV of csrc/med_pose.hip)
-MAX_PLANES = 128   # HEAD_MAXN
 OUTPUTS = ("view", "disp", "cover")
 
 
@@ -125,45 +126,24 @@ def check_want(want):
     return want
 
 
-def _f32(x, what):
-    if not x.is_cuda:
-        raise RuntimeError("fal_net_amd.freeview runs on an MI355X only (no CPU fallback); {} is on {}".format(what, x.device))
-    return x.detach().to(torch.float32).contiguous()
-
-
 def warp(dlog0, left, min_disp, max_disp, poses, want=OUTPUTS):
     """dlog0 (B, N, H, W) planar f32 logits, left (B, 3, H, W), min_disp / max_disp: B values in pixels, poses: any number of pose() records.
     -> {"view": (B, V, 3, H, W), "disp": (B, V, 1, H, W), "cover": (B, V, 1, H, W)} restricted to `want`.  Every argument is checked
     before the first launch."""
     recs = check_poses(poses)
     want = check_want(want)
-    if dlog0.dim() != 4 or left.dim() != 4:
-        raise ValueError("freeview.warp: expected dlog0 (B, N, H, W) and left (B, 3, H, W), got {} and {}".format(tuple(dlog0.shape), tuple(left.shape)))
-    B, N, H, W = dlog0.shape
-    if not 2 <= N <= MAX_PLANES:
-        raise ValueError("freeview.warp: N={} outside [2, {}]".format(N, MAX_PLANES))
-    if tuple(left.shape) != (B, 3, H, W) or min(B, H, W) < 1:
-        raise ValueError("freeview.warp: left {} does not match the logits {}".format(tuple(left.shape), tuple(dlog0.shape)))
-    if min_disp.numel() != B or max_disp.numel() != B:
-        raise ValueError("freeview.warp: min_disp / max_disp must hold one value per sample (B={})".format(B))
-    dlog0, left = _f32(dlog0, "dlog0"), _f32(left, "left")
-    mn, mx = _f32(min_disp, "min_disp").reshape(-1), _f32(max_disp, "max_disp").reshape(-1)
+    (dlog0, left, mn, mx), (B, N, H, W) = M.check_logits("freeview.warp", dlog0, min_disp, max_disp, left, with_left=True)
     V = len(recs)
     dev = dlog0.device
     chans = {"view": 3, "disp": 1, "cover": 1}
     out = {k: torch.empty(B, V, chans[k], H, W, dtype=torch.float32, device=dev) for k in want}
     lib, st = L.lib(), L.stream_ptr()
-    for v0 in range(0, V, MAX_POSES):
-        part = np.ascontiguousarray(recs[v0:v0 + MAX_POSES])
-        n = len(part)
-        whole = v0 == 0 and n == V
-        # a launch writes (B, n, ...) densely: straight into the result when it is the only one, else into a part copied to its slice
-        bufs = {k: out[k] if whole else torch.empty(B, n, chans[k], H, W, dtype=torch.float32, device=dev) for k in want}
-        L.check(lib.falnet_med_pose_fwd(L.ptr(dlog0), L.ptr(left), L.ptr(mn), L.ptr(mx), part.ctypes.data_as(ctypes.c_void_p), n,
+
+    def launch(part, bufs):
+        part = np.ascontiguousarray(part)
+        L.check(lib.falnet_med_pose_fwd(L.ptr(dlog0), L.ptr(left), L.ptr(mn), L.ptr(mx), part.ctypes.data_as(ctypes.c_void_p), len(part),
                                         L.ptr(bufs.get("view")), L.ptr(bufs.get("disp")), L.ptr(bufs.get("cover")), B, N, H, W, st), "med_pose_fwd")
-        if not whole:
-            for k in want:
-                out[k][:, v0:v0 + n].copy_(bufs[k])
+    M.launch_in_parts(recs, MAX_POSES, out, launch)
     return out
 
 
@@ -188,7 +168,7 @@ def fill_views(out, max_disp, beta=FILL_BETA, floor=2.0 ** -10):
     B, V = view.shape[:2]
     if not torch.is_tensor(max_disp) or max_disp.numel() != B:
         raise ValueError("freeview.fill_views: max_disp must hold one value per sample (B={})".format(B))
-    scale = _f32(max_disp, "max_disp").reshape(B, 1).expand(B, V).contiguous()
+    scale = M.f32(max_disp, "max_disp", "freeview").reshape(B, 1).expand(B, V).contiguous()
     filled = inpaint.fill(torch.cat([view, disp * cover], 2), cover, guide=disp, guide_scale=scale, beta=beta, floor=floor)
     return {"view": filled[:, :, :3].contiguous(), "disp": filled[:, :, 3:].contiguous()}
 
@@ -204,9 +184,7 @@ def render(model, left, min_disp, max_disp, poses, want=OUTPUTS, fill=None):
         from . import inpaint
         inpaint.check_params(fill, 2.0 ** -10)
     with torch.no_grad():
-        disp = model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)
-        B, _, H, W = left.shape
-        buf = model._plan(B, H, W, left.device).buf  # the plan this forward has just run: its buffers hold the logits until the next forward
+        buf, disp = M.forward_logits(model, left, min_disp, max_disp)
         out = warp(buf["dlog0"], buf["left"], buf["min_disp"], buf["max_disp"], recs, want if fill is None else OUTPUTS)
         if fill is not None:
             filled = fill_views(out, buf["max_disp"], beta=fill)

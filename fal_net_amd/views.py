@@ -16,10 +16,11 @@ import math
 import torch
 
 from . import _lib as L
+from . import med_logits as M
+from .med_logits import MAX_PLANES  # noqa: F401  (part of this module's interface)
 
 MAX_VIEWS = 8      # views per launch (SW_MAXV of csrc/med_sweep.hip)
 MAX_ABS_T = 2.0    # the library refuses |t| above this
-MAX_PLANES = 128   # HEAD_MAXN
 
 
 def check_baselines(baselines):
@@ -33,49 +34,24 @@ def check_baselines(baselines):
     return ts
 
 
-def _f32(x, what):
-    if not x.is_cuda:
-        raise RuntimeError("fal_net_amd.views runs on an MI355X only (no CPU fallback); {} is on {}".format(what, x.device))
-    return x.detach().to(torch.float32).contiguous()
-
-
 def sweep(dlog0, left, min_disp, max_disp, baselines, want_views=True, want_disps=True):
     """dlog0 (B, N, H, W) planar f32 logits, left (B, 3, H, W), min_disp / max_disp: B values in pixels, baselines: any number of fractions.
     -> (views (B, V, 3, H, W) or None, disps (B, V, 1, H, W) or None).  Every argument is checked before the first launch."""
     ts = check_baselines(baselines)
     if not (want_views or want_disps):
         raise ValueError("views.sweep: neither views nor disparities requested")
-    if dlog0.dim() != 4 or left.dim() != 4:
-        raise ValueError("views.sweep: expected dlog0 (B, N, H, W) and left (B, 3, H, W), got {} and {}".format(tuple(dlog0.shape), tuple(left.shape)))
-    B, N, H, W = dlog0.shape
-    if not 2 <= N <= MAX_PLANES:
-        raise ValueError("views.sweep: N={} outside [2, {}]".format(N, MAX_PLANES))
-    if tuple(left.shape) != (B, 3, H, W) or min(B, H, W) < 1:
-        raise ValueError("views.sweep: left {} does not match the logits {}".format(tuple(left.shape), tuple(dlog0.shape)))
-    if min_disp.numel() != B or max_disp.numel() != B:
-        raise ValueError("views.sweep: min_disp / max_disp must hold one value per sample (B={})".format(B))
-    dlog0, left = _f32(dlog0, "dlog0"), _f32(left, "left")
-    mn, mx = _f32(min_disp, "min_disp").reshape(-1), _f32(max_disp, "max_disp").reshape(-1)
+    (dlog0, left, mn, mx), (B, N, H, W) = M.check_logits("views.sweep", dlog0, min_disp, max_disp, left, with_left=True)
     V = len(ts)
     dev = dlog0.device
     views = torch.empty(B, V, 3, H, W, dtype=torch.float32, device=dev) if want_views else None
     disps = torch.empty(B, V, 1, H, W, dtype=torch.float32, device=dev) if want_disps else None
     lib, st = L.lib(), L.stream_ptr()
-    for v0 in range(0, V, MAX_VIEWS):
-        part = ts[v0:v0 + MAX_VIEWS]
-        n = len(part)
-        whole = v0 == 0 and n == V
-        # a launch writes (B, n, ...) densely: straight into the result when it is the only one, else into a part copied to its slice
-        pv = views if whole or views is None else torch.empty(B, n, 3, H, W, dtype=torch.float32, device=dev)
-        pd = disps if whole or disps is None else torch.empty(B, n, 1, H, W, dtype=torch.float32, device=dev)
-        t_host = (ctypes.c_float * n)(*part)
-        L.check(lib.falnet_med_sweep_fwd(L.ptr(dlog0), L.ptr(left), L.ptr(mn), L.ptr(mx), ctypes.cast(t_host, ctypes.c_void_p), n, L.ptr(pv), L.ptr(pd),
-                                         B, N, H, W, st), "med_sweep_fwd")
-        if not whole:
-            if views is not None:
-                views[:, v0:v0 + n].copy_(pv)
-            if disps is not None:
-                disps[:, v0:v0 + n].copy_(pd)
+
+    def launch(part, bufs):
+        t_host = (ctypes.c_float * len(part))(*part)
+        L.check(lib.falnet_med_sweep_fwd(L.ptr(dlog0), L.ptr(left), L.ptr(mn), L.ptr(mx), ctypes.cast(t_host, ctypes.c_void_p), len(part),
+                                         L.ptr(bufs[0]), L.ptr(bufs[1]), B, N, H, W, st), "med_sweep_fwd")
+    M.launch_in_parts(ts, MAX_VIEWS, (views, disps), launch)
     return views, disps
 
 
@@ -87,9 +63,7 @@ def render(model, left, min_disp, max_disp, baselines, want_views=True, want_dis
     if not (want_views or want_disps):
         raise ValueError("views.render: neither views nor disparities requested")
     with torch.no_grad():
-        disp = model(left, min_disp, max_disp, ret_disp=True, ret_subocc=False, ret_pan=False)
-        B, _, H, W = left.shape
-        buf = model._plan(B, H, W, left.device).buf  # the plan this forward has just run: its buffers hold the logits until the next forward
+        buf, disp = M.forward_logits(model, left, min_disp, max_disp)
         views, disps = sweep(buf["dlog0"], buf["left"], buf["min_disp"], buf["max_disp"], ts, want_views, want_disps)
     return views, disps, disp
 

@@ -119,6 +119,30 @@ def test_head_against_float64(case, family):
     assert not bad, bad
 
 
+def test_forward_of_logits_off_the_16_byte_grid():
+    """The forward on logits that start one float into their allocation (4-byte aligned, not 16): the chooser's alignment predicate sends
+    them past the second-generation kernel to med_head_fwd_lds_kernel, which fills its rows with scalar loads (as W = 77 and W = 1242 do).
+    disp and p_im0 within the bound of the aligned cases.  (No backward twin: its fallback stores 16-byte vectors.)"""
+    case = (1, 9, 2, 40, 30.0)
+    inp, ref = R.cached(case, "a")
+    B, N, H, W = inp["dlog0"].shape
+    assert head_kernel(0, torch.float32, N, W) == "med_head_fwd_lds2_kernel"  # what the aligned launch of this shape takes
+    room = torch.zeros(inp["dlog0"].numel() + 4, device=DEV)
+    d0 = room[1:1 + inp["dlog0"].numel()].view(B, N, H, W)
+    d0.copy_(inp["dlog0"])
+    assert d0.data_ptr() % 16 == 4 and d0.is_contiguous()
+    lf, mnd, mxd = inp["left"].to(DEV), inp["mn"].to(DEV), inp["mx"].to(DEV)
+    disp, pan, stats = _nan(B, 1, H, W), _nan(B, 3, H, W), _nan(B, 4, H, W)
+    P = L.ptr
+    L.check(L.lib().falnet_med_head_fwd(P(d0), P(lf), P(mnd), P(mxd), P(disp), P(pan), P(stats), B, N, H, W, L.stream_ptr()))
+    torch.cuda.synchronize()
+    for key, got in (("disp", disp), ("p_im0", pan)):
+        r = R.compare(got, ref[key], ref["mag_" + key], torch.float32, R.coef(key, case))
+        print(f"{case} unaligned {key}: coef {r['coef']:.3g} worst ratio {r['worst_ratio']:.3g} max-norm {r['maxnorm']:.3g}")
+        assert r["bad"] == 0, (key, r)
+    assert bool(torch.isfinite(stats).all())
+
+
 @pytest.mark.parametrize("case", [R.ALL_CASES[0], R.ALL_CASES[1]])
 def test_head_bound_can_fail(case):
     """Valid launches on perturbed inputs against the UNperturbed reference: min_disp (1 + 2^-10), one logit plane rolled by a pixel, and
