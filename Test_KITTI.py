@@ -21,6 +21,7 @@ their hole-filled versions, fal_net_amd/inpaint.py;
 `--sparsification SCORES [--sparsification-steps S]` writes sparsification.txt: AUSE / AURG of the named confidence scores against the depth errors,
 fal_net_amd/sparsification.py;
 `--pseudo-lidar [--pl-beams N ...]` adds each frame's depth as a Velodyne-format scan Pseudo_lidar/<frame>.bin, fal_net_amd/pseudo_lidar.py;
+`--mesh [--mesh-max-jump T ...]` adds each frame's depth as a triangle mesh Mesh/<frame>.ply, cut where depth jumps, fal_net_amd/mesh.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -261,6 +262,41 @@ def check_lidar_args(a):
         raise SystemExit('{} set(s) a parameter of --pseudo-lidar: add --pseudo-lidar'.format(', '.join('--' + n.replace('_', '-') for n in given)))
 
 
+def _max_jump(v):
+    x = float(v)
+    if not x >= 0.0:
+        raise argparse.ArgumentTypeError('--mesh-max-jump needs a number >= 0 (inf: no cut), got {}'.format(v))
+    return x
+
+
+def _mesh_max_depth(v):
+    x = float(v)
+    if not 0.0 < x < 200.0:
+        raise argparse.ArgumentTypeError('--mesh-max-depth needs 0 < M < 200 (the point cloud caps depth at 200 m), got {}'.format(v))
+    return x
+
+
+parser.add_argument('--mesh', action='store_true',
+                    help='also write each frame\'s depth as a triangle mesh Mesh/<frame>.ply: the pixel grid triangulated and cut where depth jumps, vertices and '
+                         'faces compacted on the device (fal_net_amd/mesh.py), in the format of --ply-format, and one JSON line with the counts')
+parser.add_argument('--mesh-max-jump', type=_max_jump, default=0.05, metavar='T',
+                    help='--mesh: a triangle is cut when the depths of two of its vertices differ by more than the factor 1 + T (inf: only invalid vertices cut)')
+parser.add_argument('--mesh-max-depth', type=_mesh_max_depth, default=80.0, metavar='M', help='--mesh: vertices beyond M metres are dropped')
+parser.add_argument('--mesh-min-conf', type=lambda v: _min_conf(v, '--mesh-min-conf'), default=None, metavar='C',
+                    help='--mesh: keep only the vertices whose probability mass around the arg-max plane (conf) is at least C (one more forward per frame)')
+parser.add_argument('--mesh-normals', action='store_true', help='--mesh: per-vertex normals (nx ny nz) in the file, summed over the kept triangles around a vertex')
+MESH_ARGS = ('mesh', 'mesh_max_jump', 'mesh_max_depth', 'mesh_min_conf', 'mesh_normals')
+
+
+def check_mesh_args(a):
+    """The --mesh-* switches change nothing without --mesh: SystemExit names the one that was given."""
+    if a.mesh:
+        return
+    given = [n for n in MESH_ARGS[1:] if getattr(a, n) != parser.get_default(n)]
+    if given:
+        raise SystemExit('{} set(s) a parameter of --mesh: add --mesh'.format(', '.join('--' + n.replace('_', '-') for n in given)))
+
+
 SPARSIFICATION_SCORES = ('std', 'entropy', 'conf', 'relstd')  # fal_net_amd/sparsification.py: SCORES
 
 
@@ -388,6 +424,7 @@ def main():
     check_freeview_fill_args(args)
     check_confidence_args(args)
     check_lidar_args(args)
+    check_mesh_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     check_sparsification_args(args, dataset_mode)
     model_dir = checkpoint_path(args)  # :119-120
@@ -447,6 +484,12 @@ def main():
         return pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
                                               max_height=args.pl_max_height, min_conf=args.pl_min_conf), source
 
+    mesh_writer = None
+    if args.mesh:
+        from fal_net_amd import mesh
+        mesh_writer = mesh.MeshWriter(save_path, max_jump=args.mesh_max_jump, max_depth=args.mesh_max_depth, min_conf=args.mesh_min_conf,
+                                      normals=args.mesh_normals, ply_format=args.ply_format)
+
     sparsification = None
     view = None
 
@@ -459,6 +502,8 @@ def main():
                                                  'aurg': res['sparsification']['aurg_mean'], 'file': os.path.join(save_path, 'sparsification.txt')}}))
         if lidar_writer is not None:
             print(json.dumps({'pseudo_lidar': dict(lidar_writer.summary(), calibration=lidar_source)}))
+        if mesh_writer is not None:
+            print(json.dumps({'mesh': mesh_writer.summary()}))
         if sweep_writer is not None:
             print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
         if freeview_writer is not None:
@@ -490,6 +535,7 @@ def main():
             hidden = (() if args.sweep is not None else ('sweep', 'sweep_range')) + (() if stats_writer is not None or args.disparity != 'mean' else
                                                                                   ('stats', 'pc_min_conf', 'disparity'))
             hidden += () if args.pseudo_lidar else LIDAR_ARGS
+            hidden += () if args.mesh else MESH_ARGS
             hidden += () if args.sparsification is not None else SPARSIFICATION_ARGS
             hidden += () if args.freeview is not None else FREEVIEW_ARGS
             hidden += () if args.freeview_fill is not None else FREEVIEW_FILL_ARGS
@@ -505,7 +551,7 @@ def main():
                                  with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
                                  device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
                                  disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics,
-                                 freeview_writer=freeview_writer, freeview_poses=fv_poses, freeview_fill=args.freeview_fill)
+                                 freeview_writer=freeview_writer, freeview_poses=fv_poses, freeview_fill=args.freeview_fill, mesh_writer=mesh_writer)
         if args.view_metrics:
             view = res['view']
             write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
@@ -554,6 +600,8 @@ def main():
             inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
         if lidar_writer is not None:
             inference.lidar_frame(lidar_writer, 0, pan_model, left, disp, min_disp, max_disp)
+        if mesh_writer is not None:
+            inference.mesh_frame(mesh_writer, 0, pan_model, left, disp, min_disp, max_disp)
         if args.view_metrics:
             # the timed image is seeded noise and its pair's right image is independent of it: no view metric means anything there.  The view is
             # judged on a seeded pair with real geometry instead (synthetic.structured_stereo: the right image IS the left one resampled along a

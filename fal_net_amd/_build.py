@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libfalnet_hip.so")
-SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_pose.hip", "inpaint.hip", "med_stats.hip", "compact.hip", "losses.hip", "adam.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "ssim.hip", "velo.hip", "lidar.hip", "sort.hip", "sparsify.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
+SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_pose.hip", "inpaint.hip", "med_stats.hip", "compact.hip", "losses.hip", "adam.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "ssim.hip", "velo.hip", "lidar.hip", "mesh.hip", "sort.hip", "sparsify.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  The MED head kernels are f32 VALU work per pixel and plane: the SLP vectoriser pairs independent scalar
@@ -26,12 +26,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # the host's float64 back-projection and bin search the same way: a record and its bin must be the host's bit for bit.  sparsify.hip runs
 # the depth chain of metrics.hip per pixel (csrc/depth_pair.h, whose includers all need the flag): its errors order the pixels and its d1 counts
 # are compared with numpy's as integers.  ssim.hip forms the metric's 0..255 operands in f32 as torch does (an add, a multiply, a rounding half to
-# even): contracted into a fused multiply-add, pixels cross a rounding boundary.
+# even): contracted into a fused multiply-add, pixels cross a rounding boundary.  mesh.hip runs the point cloud's f32 vertex chain (csrc/pc_vertex.h,
+# whose includers all need the flag) and sums its normals in float64 in a fixed order: a vertex record and a kept triangle must be the host's bit for bit.
 FILE_FLAGS = {"med_head.hip": ["-fno-slp-vectorize"], "med_head2.hip": ["-fno-slp-vectorize"], "med_sweep.hip": ["-fno-slp-vectorize"],
               "med_stats.hip": ["-fno-slp-vectorize"], "med_pose.hip": ["-fno-slp-vectorize"],
               "dump.hip": ["-ffp-contract=off"],
               "metrics.hip": ["-ffp-contract=off"], "ssim.hip": ["-ffp-contract=off"], "augment_batch.hip": ["-ffp-contract=off"], "velo.hip": ["-ffp-contract=off"],
-              "lidar.hip": ["-ffp-contract=off"], "sparsify.hip": ["-ffp-contract=off"]}
+              "lidar.hip": ["-ffp-contract=off"], "sparsify.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out, deps):
@@ -62,7 +63,7 @@ def build_ab(tag="ab", defines=(), verbose=True, raw=()):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "ordered.h"), os.path.join(CSRC, "depth_pair.h"), os.path.join(CSRC, "med_planes.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "ordered.h"), os.path.join(CSRC, "depth_pair.h"), os.path.join(CSRC, "med_planes.h"), os.path.join(CSRC, "pc_vertex.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
     jobs = []
     for src in SOURCES:
         path = os.path.join(CSRC, src)

@@ -10,6 +10,7 @@
 // None of this is on the training step's path and none of it is part of the autotune key (ops.py: _TUNE_SOURCES).
 #include "common.h"
 #include "ordered.h"
+#include "pc_vertex.h"
 
 // ---- exact percentile: radix select over the monotone integer image of the floats -----------------------------------------------------
 // key_f32(x) (ordered.h) is monotone in x (negative floats: all bits flipped; others: sign bit set), so the k-th smallest float is the k-th
@@ -271,30 +272,7 @@ extern "C" int falnet_local_norm(const float* x, float mean_r, float mean_g, flo
 }
 
 // ---- point cloud (myUtils.py:339-373) ----------------------------------------------------------------------------------------------------
-struct PcParams {
-    float m0, m1, m2, rgb_scale;  // colour = (img + mean) * rgb_scale
-    float focal, fb;              // fb = focal * baseline, formed in double by the caller and rounded once (as torch does with the Python product)
-    float cx, cy;                 // w / 2, h / 2
-    int H, W;
-};
-struct PcVertex { float x, z, ny, r, g, b; };
-
-// vertex g of the batch (g = b * H * W + i * W + j)
-__device__ __forceinline__ PcVertex pc_vertex(const float* __restrict__ img, const float* __restrict__ disp, const PcParams& p, uint32_t g) {
-    const uint32_t hw = (uint32_t)p.H * p.W, b = g / hw, pix = g - b * hw, i = pix / p.W, j = pix - i * p.W;
-    float z = __fdiv_rn(p.fb, __fadd_rn(disp[g], 1e-4f));
-    const float u = (float)j + 0.5f, v = (float)i + 0.5f;  // affine_grid, align_corners=False: (grid + 1) / 2 * w
-    PcVertex o;
-    o.x = __fmul_rn(__fdiv_rn(u - p.cx, p.focal), z);  // from the UNCAPPED z
-    o.ny = -__fmul_rn(__fdiv_rn(v - p.cy, p.focal), z);
-    z = z < 0.f ? 0.f : z;
-    o.z = z > 200.f ? 200.f : z;
-    const float* c = img + (size_t)b * 3 * hw + pix;
-    o.r = __fmul_rn(__fadd_rn(c[0], p.m0), p.rgb_scale);
-    o.g = __fmul_rn(__fadd_rn(c[hw], p.m1), p.rgb_scale);
-    o.b = __fmul_rn(__fadd_rn(c[2 * (size_t)hw], p.m2), p.rgb_scale);
-    return o;
-}
+// PcParams, PcVertex, pc_vertex and trunc_u8: csrc/pc_vertex.h, shared with mesh.hip
 
 // rows x, z, -y, r, g, b of (B, 6, H W): one vertex per thread, every store coalesced
 __global__ __launch_bounds__(256) void point_cloud_planar_kernel(const float* __restrict__ img, const float* __restrict__ disp, PcParams p, float* __restrict__ out,
@@ -307,9 +285,6 @@ __global__ __launch_bounds__(256) void point_cloud_planar_kernel(const float* __
         o[0] = v.x, o[hw] = v.z, o[2 * (size_t)hw] = v.ny, o[3 * (size_t)hw] = v.r, o[4 * (size_t)hw] = v.g, o[5 * (size_t)hw] = v.b;
     }
 }
-
-// int() of the reference (truncation toward zero), saturated to a byte
-__device__ __forceinline__ uint32_t trunc_u8(float v) { return v >= 255.f ? 255u : (v >= 1.f ? (uint32_t)v : 0u); }
 
 // `val` at byte offset `off` of the little-endian dword array w (off is a compile-time constant after unrolling: all of this folds to registers)
 __device__ __forceinline__ void put_bits(uint32_t (&w)[15], int off, uint32_t val, int nbytes) {

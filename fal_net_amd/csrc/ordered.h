@@ -1,6 +1,6 @@
 // Primitives whose result is decided by indices and integers alone, written ONCE for the evaluation-side kernels that the tests hold bit for
 // bit: the monotone integer image of a float (dump.hip, velo.hip, metrics.hip, sparsify.hip), the f64 sum over a wave (metrics.hip,
-// sparsify.hip) and the pieces of the ordered compaction -- count, ONE offset scan, scatter -- of compact.hip, lidar.hip and sparsify.hip
+// sparsify.hip) and the pieces of the ordered compaction -- count, ONE offset scan, scatter -- of compact.hip, lidar.hip, sparsify.hip and mesh.hip
 // (DESIGN.md section 7d).  Device code is __forceinline__ and there is no __global__ in this file: the one scan kernel lives in compact.hip.
 // Not part of common.h on purpose: that file is hashed into the autotune cache header (ops.py: _TUNE_SOURCES), this one is not.
 #pragma once

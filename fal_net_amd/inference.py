@@ -3,7 +3,7 @@ The resampling of the 1- and 3-channel maps (bilinear x2/3, nearest back) goes t
 host-side 95th percentile stays in numpy exactly as in the reference (opt-in: the exact device-side percentile of dumps.py); the two
 network forwards are the HIP plan.  `evaluate(writer=...)` also writes every frame's outputs to disk (dumps.FrameWriter), `evaluate(sweep_writer=...)` its views along the
 baseline (dumps.SweepWriter), `evaluate(freeview_writer=...)` its free-viewpoint views (freeview.FreeviewWriter), `evaluate(stats_writer=...)` the statistics of its disparity distribution and its confidence-filtered point cloud
-(confidence.StatsWriter), `evaluate(lidar_writer=...)` its disparity back-projected into a Velodyne-format scan (pseudo_lidar.PseudoLidarWriter);
+(confidence.StatsWriter), `evaluate(lidar_writer=...)` its disparity back-projected into a Velodyne-format scan (pseudo_lidar.PseudoLidarWriter), `evaluate(mesh_writer=...)` its disparity as a triangle mesh cut at its depth edges (mesh.MeshWriter);
 `evaluate(sparsification=...)` the sparsification curves of its confidence scores against its depth errors (sparsification.SparsificationTable);
 `evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
 import math
@@ -107,6 +107,16 @@ def lidar_frame(lidar_writer, i, pan_model, left, disp, min_disp, max_pix):
     lidar_writer.write(i, disp, P, fb, conf=conf)
 
 
+def mesh_frame(mesh_writer, i, pan_model, left, disp, min_disp, max_pix):
+    """Frame `i` through a mesh.MeshWriter: `disp`, the disparity the run evaluates, as a triangle mesh cut at its depth edges.  The confidence
+    map comes from one more disparity-only forward (confidence.from_model), only when the writer filters by it."""
+    conf = None
+    if mesh_writer.min_conf is not None:
+        from . import confidence
+        conf = confidence.from_model(pan_model, left, min_disp, max_pix, ("conf",))[0]["conf"]
+    mesh_writer.write(i, left, disp, conf=conf)
+
+
 def sparsify_frame(table, pan_model, left, disp, target, mode, use_median, min_disp, max_pix):
     """One frame with ground truth into the next row of a sparsification.SparsificationTable.  The errors are those of `disp`, the disparity the
     run evaluates AFTER post-processing; the scores (table.names, from sparsification.SCORES) are statistics of the logits of one more
@@ -144,7 +154,7 @@ def peak_disparity(pan_model, left, min_disp, max_pix):
 def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=2.0, rel_baseline=1.0, post="ms_pp", use_median=False,
              print_freq=10, log=print, with_metrics=True, writer=None, device_percentile=False, device_metrics=False, sweep_writer=None,
              sweep_fractions=None, stats_writer=None, disparity="mean", lidar_writer=None, sparsification=None, view_metrics=False,
-             freeview_writer=None, freeview_poses=None, freeview_fill=None):
+             freeview_writer=None, freeview_poses=None, freeview_fill=None, mesh_writer=None):
     """The evaluation loop of Test_KITTI.py:163-208,255-280 over a loader of full-size frames (batch size 1: KITTI mixes image
     sizes, :113): forward (+ flip or multi-scale post-processing, :196-205), then per image the KITTI depth errors and -- for
     KITTI 2015 -- the end-point error (:257-271).  `loader` yields lists of (left_u8, right_u8, gt) from
@@ -161,6 +171,7 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
     freeview_fill: a bias beta -- their hole-filled versions as well (freeview.fill_views).
     stats_writer: a confidence.StatsWriter -- every frame's distribution statistics and its confidence-filtered point cloud are written too (stats_frame).
     lidar_writer: a pseudo_lidar.PseudoLidarWriter -- every frame's disparity is also written as a Velodyne-format scan (lidar_frame).
+    mesh_writer: a mesh.MeshWriter -- every frame's disparity is also written as a triangle mesh cut at its depth edges (mesh_frame).
     sparsification: a sparsification.SparsificationTable built with the score names -- every frame with ground truth also leaves its sparsification
     curves in the table's next row (sparsify_frame: the errors of `disp` after post-processing, the scores from one more disparity-only forward), with
     and without device_metrics; the table is read once after the last frame and its result() is returned under 'sparsification'.
@@ -238,6 +249,8 @@ def evaluate(pan_model, loader, data_name="Kitti2015", max_disp=300.0, min_disp=
                     stats_frame(stats_writer, n, pan_model, left, disp, mn, mx)
                 if lidar_writer is not None:
                     lidar_frame(lidar_writer, n, pan_model, left, disp, mn, mx)
+                if mesh_writer is not None:
+                    mesh_frame(mesh_writer, n, pan_model, left, disp, mn, mx)
                 n += 1
             if log is not None and i % print_freq == 0:
                 a1 = kitti.avg[4] if table is None else table.running_mean("a1")

@@ -825,6 +825,40 @@ int falnet_velo_unproject(const float* map, double fb, const float* score, float
                           float min_depth, float max_depth, float max_height, int H, int W, int beams, int az_bins, const double* elev_edges_dev,
                           const double* az_edges_dev, float* out_points, int64_t capacity, int64_t* count_dev, void* workspace, void* stream);
 
+/* ---- Triangle mesh of the predicted depth (csrc/mesh.hip; fal_net_amd/mesh.py) ------------------------------------------------------------------
+ * One sample's pixel grid triangulated and cut where depth jumps, as binary-PLY records (the numpy restatement is tests/_mesh_ref.py).
+ * img (3 x H x W planar f32), means, rgb_scale, disp (H x W f32), focal, baseline: as falnet_point_cloud with B = 1 -- vertex g = i W + j IS that
+ * cloud's vertex (csrc/pc_vertex.h): z = fb / (disp + 1e-4f), x and -y from the uncapped z, z capped to [0, 200], colour (img + mean) rgb_scale
+ * truncated and saturated to a byte.
+ *   valid vertex   min_depth < z && z <= max_depth on the capped f32 z, and with score (H x W f32, may be NULL) score >= threshold; every comparison
+ *                  with a NaN is false.  0 <= min_depth < max_depth < 200, so a valid vertex is never a capped one.
+ *   quad (i, j)    0 <= i < H - 1, 0 <= j < W - 1, corners a = (i, j), b = (i, j + 1), c = (i + 1, j), d = (i + 1, j + 1).  Two or more invalid corners:
+ *                  no triangle.  One: the diagonal that avoids it (a or d invalid: b-c; b or c invalid: a-d).  None: a-d iff |za - zd| <= |zb - zc|
+ *                  (f32 subtractions; a tie goes to a-d), else b-c.
+ *   triangles      diagonal a-d: T0 = (a, c, d), T1 = (a, d, b); diagonal b-c: T0 = (a, c, b), T1 = (b, c, d).  With PLY axes x right, y forward, z up
+ *                  (the record's x, z, -y) every (v1 - v0) x (v2 - v0) points towards the camera.
+ *   keep rule      a triangle is kept iff its three vertices are valid and each edge (p, q) has max(zp, zq) <= min(zp, zq) * ratio: one correctly
+ *                  rounded f32 multiply, ratio = (float)(1.0 + max_jump) formed in double and rounded once.  max_jump >= 0; infinity keeps every
+ *                  valid triangle.
+ *   vertices_out   the vertices named by a kept triangle, in pixel order: 15-byte records x y z f32, r g b u8 (fal_net_amd/dumps.py: PLY_VERTEX) or,
+ *                  with_normals != 0, 27-byte records x y z nx ny nz f32, r g b u8.  Room for H W records.
+ *   faces_out      the kept triangles in quad order, T0 before T1: 13-byte records, the byte 3 and three little-endian int32 indices into
+ *                  vertices_out (a vertex's index is its rank among the used pixels).  Room for 2 (H - 1) (W - 1) records.
+ *   normal         of a used vertex: the sum, over the kept triangles that contain it, of the un-normalised (V1 - V0) x (V2 - V0) in the triangle's
+ *                  stored vertex order, taken over the quads (i - 1, j - 1), (i - 1, j), (i, j - 1), (i, j) in that order, T0 before T1; f64 from the f32
+ *                  record coordinates, each component two products and a subtraction, no fused multiply-add; len = sqrt((nx nx + ny ny) + nz nz);
+ *                  each of nx / len, ny / len, nz / len is divided in f64 and rounded to f32; (0, 0, 0) when len is zero or not finite.  A gather: no
+ *                  scatter, no atomic.
+ * counts_dev: two int64 on the device, the number of vertex and of face records.  Bytes beyond the records are not touched; positions are decided by
+ * indices alone (csrc/ordered.h), so two calls give the same bytes.  workspace: falnet_mesh_workspace_bytes(H, W) bytes, 8-byte aligned as counts_dev;
+ * img, disp, score and the two outputs 4-byte aligned.  H < 2 or W < 2 is legal: counts (0, 0), nothing else written.  Refused with nothing launched:
+ * a NULL img, disp, output, counts_dev or workspace, H W < 1 or >= 2^28, focal <= 0, min_depth / max_depth outside the stated order (a NaN included),
+ * a negative or NaN max_jump, a misaligned pointer.  falnet_mesh_workspace_bytes is 0 for a refused shape.  One sample per call.  Not replayable. */
+int64_t falnet_mesh_workspace_bytes(int H, int W);
+int falnet_mesh_build(const float* img, float mean_r, float mean_g, float mean_b, float rgb_scale, const float* disp, double focal, double baseline,
+                      const float* score, float threshold, float min_depth, float max_depth, double max_jump, int H, int W, int with_normals,
+                      void* vertices_out, void* faces_out, int64_t* counts_dev, void* workspace, void* stream);
+
 /* ---- stable segmented argsort (csrc/sort.hip; fal_net_amd/sparsification.py: argsort_u32) ---------------------------------------------------
  * keys: `segments` independent arrays of n u32 keys each, keys[s * n + i], 1 <= segments <= 8, n <= 2^24, on the device, never written.
  * perm[s * n + r] = the index i of the element of segment s that has rank r in ascending key order; equal keys stay in ascending index order
