@@ -99,15 +99,20 @@ parser.add_argument('--iters', type=int, default=10)
 parser.add_argument('--dtype', default='f16', choices=['f16', 'bf16', 'f32'])
 
 
-def _dump_kinds(v):
-    kinds = [k for k in v.split(',') if k]
-    bad = [k for k in kinds if k not in ('disp', 'input', 'pan', 'pc', 'feats')]
-    if bad:
-        raise argparse.ArgumentTypeError('unknown dump kind(s) {}: choose from disp,input,pan,pc,feats'.format(','.join(bad)))
-    return kinds
+def _comma_list(choices, message, strict):
+    """argparse type of a comma-separated subset of `choices`, as a list in the order given.  strict: an empty list and a repeated name are
+    refused as well.  message: the error's text, formatted with bad (the unknown names), choices and v (the value as given)."""
+    def parse(v):
+        names = [k for k in v.split(',') if k]
+        bad = [k for k in names if k not in choices]
+        if bad or (strict and (not names or len(set(names)) != len(names))):
+            raise argparse.ArgumentTypeError(message.format(bad=','.join(bad), choices=','.join(choices), v=v))
+        return names
+    return parse
 
 
-parser.add_argument('--dump', type=_dump_kinds, default=[], metavar='KINDS',
+DUMP_KINDS = ('disp', 'input', 'pan', 'pc', 'feats')  # fal_net_amd/dumps.py: DUMP_KINDS
+parser.add_argument('--dump', type=_comma_list(DUMP_KINDS, 'unknown dump kind(s) {bad}: choose from {choices}', strict=False), default=[], metavar='KINDS',
                     help='comma-separated subset of disp,input,pan,pc,feats: per-frame outputs of the reference\'s test script (:211-253) written under the '
                          'save path in its folders (l_disp, "Input im", Pan, Point_cloud, feats), finished on the GPU; --synthetic dumps its one frame')
 parser.add_argument('--ply-format', default='binary', choices=['binary', 'ascii'], help='point clouds: binary_little_endian records, or the reference\'s ASCII file')
@@ -192,25 +197,21 @@ def freeview_poses(a):
 STATS_KINDS = ('std', 'entropy', 'arg', 'conf', 'peak')
 
 
-def _stats_kinds(v):
-    kinds = [k for k in v.split(',') if k]
-    bad = [k for k in kinds if k not in STATS_KINDS]
-    if bad or not kinds or len(set(kinds)) != len(kinds):
-        raise argparse.ArgumentTypeError('--stats takes a comma-separated subset of {} (each once), got {!r}'.format(','.join(STATS_KINDS), v))
-    return kinds
+def _min_conf(name):
+    def parse(v):
+        from fal_net_amd.confidence import check_min_conf
+        try:
+            return check_min_conf(float(v), name)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+    return parse
 
 
-def _min_conf(v, name='--pc-min-conf'):
-    c = float(v)
-    if not 0.0 < c <= 1.0:
-        raise argparse.ArgumentTypeError('{} needs 0 < C <= 1, got {}'.format(name, v))
-    return c
-
-
-parser.add_argument('--stats', type=_stats_kinds, default=None, metavar='KINDS',
+parser.add_argument('--stats', type=_comma_list(STATS_KINDS, '--stats takes a comma-separated subset of {choices} (each once), got {v!r}', strict=True),
+                    default=None, metavar='KINDS',
                     help='comma-separated subset of std,entropy,arg,conf,peak: per-pixel statistics of each frame\'s distribution over the disparity planes '
                          '(fal_net_amd/confidence.py: one fused launch over the logits) as stats/<frame>_<kind>.png, and one JSON line with their means')
-parser.add_argument('--pc-min-conf', type=_min_conf, default=None, metavar='C',
+parser.add_argument('--pc-min-conf', type=_min_conf('--pc-min-conf'), default=None, metavar='C',
                     help='with --dump pc: Point_cloud/<frame>.ply holds only the vertices whose probability mass around the arg-max plane (conf) is at least C')
 parser.add_argument('--disparity', default='mean', choices=['mean', 'peak'],
                     help='the disparity that is evaluated and dumped: the expectation over all planes, or the expectation over the arg-max plane and its '
@@ -243,23 +244,12 @@ parser.add_argument('--pl-beams', type=_int_in('--pl-beams', 0, 128), default=0,
 parser.add_argument('--pl-az-bins', type=_int_in('--pl-az-bins', 1, 4096), default=1024, metavar='N', help='--pseudo-lidar with --pl-beams: azimuth bins over -45..45 degrees')
 parser.add_argument('--pl-max-depth', type=_positive('--pl-max-depth'), default=80.0, metavar='M', help='--pseudo-lidar: points beyond M metres are dropped')
 parser.add_argument('--pl-max-height', type=float, default=1.0, metavar='M', help='--pseudo-lidar: points higher than M metres above the sensor are dropped (inf: none)')
-parser.add_argument('--pl-min-conf', type=lambda v: _min_conf(v, '--pl-min-conf'), default=None, metavar='C',
+parser.add_argument('--pl-min-conf', type=_min_conf('--pl-min-conf'), default=None, metavar='C',
                     help='--pseudo-lidar: keep only the pixels whose probability mass around the arg-max plane (conf) is at least C (one more forward per frame)')
 parser.add_argument('--pl-calib', default=None, metavar='DIR',
                     help='--pseudo-lidar: directory holding calib_cam_to_cam.txt and calib_velo_to_cam.txt for every frame.  Default: each frame\'s own date with '
                          '-tn Kitti_eigen_test_original --velodyne-root, else a nominal pinhole camera at the image centre')
 LIDAR_ARGS = ('pseudo_lidar', 'pl_beams', 'pl_az_bins', 'pl_max_depth', 'pl_max_height', 'pl_min_conf', 'pl_calib')
-
-
-def check_lidar_args(a):
-    """The --pl-* switches change nothing without --pseudo-lidar: SystemExit names the one that was given."""
-    if a.pseudo_lidar:
-        if a.pl_max_height != a.pl_max_height:
-            raise SystemExit('--pl-max-height is not a number')
-        return
-    given = [n for n in LIDAR_ARGS[1:] if getattr(a, n) != parser.get_default(n)]
-    if given:
-        raise SystemExit('{} set(s) a parameter of --pseudo-lidar: add --pseudo-lidar'.format(', '.join('--' + n.replace('_', '-') for n in given)))
 
 
 def _max_jump(v):
@@ -282,33 +272,16 @@ parser.add_argument('--mesh', action='store_true',
 parser.add_argument('--mesh-max-jump', type=_max_jump, default=0.05, metavar='T',
                     help='--mesh: a triangle is cut when the depths of two of its vertices differ by more than the factor 1 + T (inf: only invalid vertices cut)')
 parser.add_argument('--mesh-max-depth', type=_mesh_max_depth, default=80.0, metavar='M', help='--mesh: vertices beyond M metres are dropped')
-parser.add_argument('--mesh-min-conf', type=lambda v: _min_conf(v, '--mesh-min-conf'), default=None, metavar='C',
+parser.add_argument('--mesh-min-conf', type=_min_conf('--mesh-min-conf'), default=None, metavar='C',
                     help='--mesh: keep only the vertices whose probability mass around the arg-max plane (conf) is at least C (one more forward per frame)')
 parser.add_argument('--mesh-normals', action='store_true', help='--mesh: per-vertex normals (nx ny nz) in the file, summed over the kept triangles around a vertex')
 MESH_ARGS = ('mesh', 'mesh_max_jump', 'mesh_max_depth', 'mesh_min_conf', 'mesh_normals')
 
 
-def check_mesh_args(a):
-    """The --mesh-* switches change nothing without --mesh: SystemExit names the one that was given."""
-    if a.mesh:
-        return
-    given = [n for n in MESH_ARGS[1:] if getattr(a, n) != parser.get_default(n)]
-    if given:
-        raise SystemExit('{} set(s) a parameter of --mesh: add --mesh'.format(', '.join('--' + n.replace('_', '-') for n in given)))
-
-
 SPARSIFICATION_SCORES = ('std', 'entropy', 'conf', 'relstd')  # fal_net_amd/sparsification.py: SCORES
 
-
-def _sparsification_scores(v):
-    names = [k for k in v.split(',') if k]
-    bad = [k for k in names if k not in SPARSIFICATION_SCORES]
-    if bad or not names or len(set(names)) != len(names):
-        raise argparse.ArgumentTypeError('--sparsification takes a comma-separated subset of {} (each once), got {!r}'.format(','.join(SPARSIFICATION_SCORES), v))
-    return names
-
-
-parser.add_argument('--sparsification', type=_sparsification_scores, default=None, metavar='SCORES',
+parser.add_argument('--sparsification', type=_comma_list(SPARSIFICATION_SCORES, '--sparsification takes a comma-separated subset of {choices} (each once), got {v!r}',
+                                                         strict=True), default=None, metavar='SCORES',
                     help='comma-separated subset of std,entropy,conf,relstd: per frame with ground truth, remove the pixels in order of each score and of the true '
                          'error and recompute abs_rel, rms and d1 = 1 - a1 on the rest (fal_net_amd/sparsification.py: sorted and summed on the device); writes '
                          'sparsification.txt with AUSE and AURG per score and the mean curves, and one JSON line.  Dataset mode with -eval True only')
@@ -317,11 +290,42 @@ parser.add_argument('--sparsification-steps', type=_int_in('--sparsification-ste
 SPARSIFICATION_ARGS = ('sparsification', 'sparsification_steps')
 
 
+SWEEP_ARGS = ('sweep', 'sweep_range')
+STATS_ARGS = ('stats', 'pc_min_conf', 'disparity')
+# One row per family of switches: (the switch, the family's names in settings.txt with the switch's own first, is the family on?, are its
+# parameters refused without the switch?).  The --stats family has three switches of equal standing and no parameters.
+FAMILIES = (
+    ('--sweep', SWEEP_ARGS, lambda a: a.sweep is not None, False),
+    ('--stats', STATS_ARGS, lambda a: a.stats is not None or a.pc_min_conf is not None or a.disparity != 'mean', False),
+    ('--pseudo-lidar', LIDAR_ARGS, lambda a: a.pseudo_lidar, True),
+    ('--mesh', MESH_ARGS, lambda a: a.mesh, True),
+    ('--sparsification', SPARSIFICATION_ARGS, lambda a: a.sparsification is not None, True),
+    ('--freeview', FREEVIEW_ARGS, lambda a: a.freeview is not None, False),
+    ('--freeview-fill', FREEVIEW_FILL_ARGS, lambda a: a.freeview_fill is not None, False),
+)
+
+
+def hidden_settings(a):
+    """The names settings.txt leaves out: those of every family that is off, so that a run without a family writes the file it wrote before the
+    family existed."""
+    return tuple(n for _, names, on, _ in FAMILIES if not on(a) for n in names)
+
+
+def check_family_args(a):
+    """A family's parameters change nothing without its switch: SystemExit names the ones that were given (the families whose parameters are
+    refused; --sweep-range and the --freeview path parameters are accepted in silence)."""
+    for switch, names, on, strict in FAMILIES:
+        given = [] if on(a) or not strict else [n for n in names[1:] if getattr(a, n) != parser.get_default(n)]
+        if given:
+            raise SystemExit('{} {} a parameter of {}: add {}'.format(', '.join('--' + n.replace('_', '-') for n in given),
+                                                                       'sets' if len(names) == 2 else 'set(s)', switch, switch))
+    if a.pseudo_lidar and a.pl_max_height != a.pl_max_height:
+        raise SystemExit('--pl-max-height is not a number')
+
+
 def check_sparsification_args(a, dataset_mode):
-    """--sparsification needs ground truth; --sparsification-steps changes nothing without it.  SystemExit says which."""
+    """--sparsification needs ground truth.  SystemExit says which."""
     if a.sparsification is None:
-        if a.sparsification_steps is not None:
-            raise SystemExit('--sparsification-steps sets a parameter of --sparsification: add --sparsification')
         return
     if not dataset_mode:
         raise SystemExit('--sparsification compares the scores with the depth errors, and synthetic mode has no ground truth: give a dataset (-d <root>)')
@@ -412,6 +416,25 @@ def refuse_out_of_scope(a):
                          'run without them to evaluate'.format(', '.join('-' + n for n in on)))
 
 
+LINE_ORDER = ('view', 'sparsification', 'pseudo_lidar', 'mesh', 'sweep', 'freeview', 'stats')  # of the products' JSON lines, as they were added
+
+
+def extra_lines(products):
+    """One JSON line {key: summary()} per product that has a summary, with what the product wants beside its key."""
+    lines = {p.key: dict({p.key: p.summary()}, **getattr(p, 'beside', {})) for p in products if hasattr(p, 'summary')}
+    for key in LINE_ORDER:
+        if key in lines:
+            print(json.dumps(lines[key]))
+
+
+def write_tables(save_path, results):
+    """view_errors.txt and sparsification.txt from the products' results, where the run has them."""
+    if 'view' in results:
+        write_view_errors(os.path.join(save_path, 'view_errors.txt'), results['view'])
+    if 'sparsification' in results:
+        write_sparsification(os.path.join(save_path, 'sparsification.txt'), results['sparsification'])
+
+
 def main():
     import torch
     from fal_net_amd import inference, synthetic
@@ -423,8 +446,7 @@ def main():
     refuse_out_of_scope(args)
     check_freeview_fill_args(args)
     check_confidence_args(args)
-    check_lidar_args(args)
-    check_mesh_args(args)
+    check_family_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     check_sparsification_args(args, dataset_mode)
     model_dir = checkpoint_path(args)  # :119-120
@@ -444,77 +466,52 @@ def main():
     n_params = utils.get_n_params(pan_model)
     save_path = args.save_path or (os.path.join('Test_Results', args.tdataName, args.model, args.time_stamp)  # :81-85
                                    + ('fpp' if args.f_post_process else '') + ('mspp' if args.ms_post_process else ''))
-    writer = None
-    if args.dump:
-        from fal_net_amd import dumps
-        # with --pc-min-conf the point cloud is the stats writer's: the frame writer keeps the other kinds
-        writer = dumps.FrameWriter(save_path, [k for k in args.dump if k != 'pc' or args.pc_min_conf is None], ply_format=args.ply_format)
-    fractions, sweep_writer = sweep_fractions(args), None
-    if fractions is not None:
-        from fal_net_amd import dumps, views
-        try:
-            views.check_baselines(fractions)
-        except ValueError as e:
-            raise SystemExit('--sweep-range: {}'.format(e))
-        sweep_writer = dumps.SweepWriter(save_path)
 
-    fv_poses, freeview_writer = freeview_poses(args), None
-    if fv_poses is not None:
-        from fal_net_amd import freeview
-        try:
-            K = freeview.camera(args.height, args.width)
-            freeview.check_poses([freeview.pose(K, **kw) for kw in fv_poses])
-        except ValueError as e:
-            raise SystemExit('--freeview: {}'.format(e))
-        freeview_writer = freeview.FreeviewWriter(save_path)
-
-    stats_writer = None
-    if args.stats is not None or args.pc_min_conf is not None:
-        from fal_net_amd import confidence
-        stats_writer = confidence.StatsWriter(save_path, args.stats or (), pc_min_conf=args.pc_min_conf, ply_format=args.ply_format)
-
-    lidar_writer = lidar_source = None
-
-    def make_lidar_writer(triples=None):
-        from fal_net_amd import pseudo_lidar
-        calibration, source = lidar_calibration(args, triples)
-        if source == 'nominal':
-            print('=> pseudo-LiDAR: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
-                  'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
-        return pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
-                                              max_height=args.pl_max_height, min_conf=args.pl_min_conf), source
-
-    mesh_writer = None
-    if args.mesh:
-        from fal_net_amd import mesh
-        mesh_writer = mesh.MeshWriter(save_path, max_jump=args.mesh_max_jump, max_depth=args.mesh_max_depth, min_conf=args.mesh_min_conf,
-                                      normals=args.mesh_normals, ply_format=args.ply_format)
-
-    sparsification = None
-    view = None
-
-    def extra_lines():
-        if view is not None:
-            print(json.dumps({'view': view, 'file': os.path.join(save_path, 'view_errors.txt')}))
-        if sparsification is not None:
-            print(json.dumps({'sparsification': {'scores': res['sparsification']['names'], 'steps': res['sparsification']['steps'],
-                                                 'frames': res['sparsification']['frames'], 'ause': res['sparsification']['ause_mean'],
-                                                 'aurg': res['sparsification']['aurg_mean'], 'file': os.path.join(save_path, 'sparsification.txt')}}))
-        if lidar_writer is not None:
-            print(json.dumps({'pseudo_lidar': dict(lidar_writer.summary(), calibration=lidar_source)}))
-        if mesh_writer is not None:
-            print(json.dumps({'mesh': mesh_writer.summary()}))
-        if sweep_writer is not None:
-            print(json.dumps({'sweep': {'views': args.sweep, 'range': list(args.sweep_range), 'files': sweep_writer.files}}))
-        if freeview_writer is not None:
-            fv_line = dict(freeview_writer.summary(), poses=args.freeview, path=args.freeview_path, amp=list(args.freeview_amp), yaw=args.freeview_yaw,
-                           camera='nominal')
+    def make_products(triples=None):
+        """The run's products, in the order every frame goes through them (inference.run_products).  triples: the frames of dataset mode."""
+        from fal_net_amd import confidence, dumps, freeview, mesh, pseudo_lidar, views
+        from fal_net_amd import sparsification as SP
+        n_frames, products = len(triples) if triples else 1, []
+        if args.sparsification is not None:
+            products.append(SP.SparsificationTable(n_frames, args.sparsification, args.sparsification_steps or SP.DEFAULT_STEPS, dev,
+                                                   extra={'file': os.path.join(save_path, 'sparsification.txt')}))
+        if args.view_metrics:
+            products.append(inference.ViewMetrics(n_frames, dev, beside={'file': os.path.join(save_path, 'view_errors.txt')}))
+        if args.dump:
+            # with --pc-min-conf the point cloud is the stats writer's: the frame writer keeps the other kinds
+            products.append(dumps.FrameWriter(save_path, [k for k in args.dump if k != 'pc' or args.pc_min_conf is None], ply_format=args.ply_format))
+        fractions = sweep_fractions(args)
+        if fractions is not None:
+            try:
+                views.check_baselines(fractions)
+            except ValueError as e:
+                raise SystemExit('--sweep-range: {}'.format(e))
+            products.append(dumps.SweepWriter(save_path, fractions, extra={'views': args.sweep, 'range': list(args.sweep_range)}))
+        poses = freeview_poses(args)
+        if poses is not None:
+            try:
+                K = freeview.camera(args.height, args.width)
+                freeview.check_poses([freeview.pose(K, **kw) for kw in poses])
+            except ValueError as e:
+                raise SystemExit('--freeview: {}'.format(e))
+            extra = {'poses': args.freeview, 'path': args.freeview_path, 'amp': list(args.freeview_amp), 'yaw': args.freeview_yaw, 'camera': 'nominal'}
             if args.freeview_fill is not None:
                 from fal_net_amd import inpaint
-                fv_line['fill'] = {'beta': args.freeview_fill, 'floor': inpaint.FLOOR, 'levels': inpaint.levels(args.height, args.width)}
-            print(json.dumps({'freeview': fv_line}))
-        if stats_writer is not None:
-            print(json.dumps({'stats': stats_writer.summary()}))
+                extra['fill'] = {'beta': args.freeview_fill, 'floor': inpaint.FLOOR, 'levels': inpaint.levels(args.height, args.width)}
+            products.append(freeview.FreeviewWriter(save_path, poses, fill_beta=args.freeview_fill, extra=extra))
+        if args.stats is not None or args.pc_min_conf is not None:
+            products.append(confidence.StatsWriter(save_path, args.stats or (), pc_min_conf=args.pc_min_conf, ply_format=args.ply_format))
+        if args.pseudo_lidar:
+            calibration, source = lidar_calibration(args, triples)
+            if source == 'nominal':
+                print('=> pseudo-LiDAR: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
+                      'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
+            products.append(pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
+                                                           max_height=args.pl_max_height, min_conf=args.pl_min_conf, extra={'calibration': source}))
+        if args.mesh:
+            products.append(mesh.MeshWriter(save_path, max_jump=args.mesh_max_jump, max_depth=args.mesh_max_depth, min_conf=args.mesh_min_conf,
+                                            normals=args.mesh_normals, ply_format=args.ply_format))
+        return products
 
     if dataset_mode:
         from fal_net_amd import datasets as DS
@@ -532,31 +529,15 @@ def main():
         loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            hidden = (() if args.sweep is not None else ('sweep', 'sweep_range')) + (() if stats_writer is not None or args.disparity != 'mean' else
-                                                                                  ('stats', 'pc_min_conf', 'disparity'))
-            hidden += () if args.pseudo_lidar else LIDAR_ARGS
-            hidden += () if args.mesh else MESH_ARGS
-            hidden += () if args.sparsification is not None else SPARSIFICATION_ARGS
-            hidden += () if args.freeview is not None else FREEVIEW_ARGS
-            hidden += () if args.freeview_fill is not None else FREEVIEW_FILL_ARGS
+            hidden = hidden_settings(args)
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
-        if args.pseudo_lidar:
-            lidar_writer, lidar_source = make_lidar_writer(triples)
-        if args.sparsification is not None:
-            from fal_net_amd import sparsification as SP
-            sparsification = SP.SparsificationTable(len(triples), args.sparsification, args.sparsification_steps or SP.DEFAULT_STEPS, dev)
+        products = make_products(triples)
         res = inference.evaluate(pan_model, loader, data_name=args.tdataName, max_disp=args.max_disp, min_disp=args.min_disp,
                                  rel_baseline=args.rel_baselne, post=post, use_median=args.median, print_freq=args.print_freq,
-                                 with_metrics=args.evaluate, writer=writer, device_percentile=args.device_percentile,
-                                 device_metrics=args.device_metrics, sweep_writer=sweep_writer, sweep_fractions=fractions, stats_writer=stats_writer,
-                                 disparity=args.disparity, lidar_writer=lidar_writer, sparsification=sparsification, view_metrics=args.view_metrics,
-                                 freeview_writer=freeview_writer, freeview_poses=fv_poses, freeview_fill=args.freeview_fill, mesh_writer=mesh_writer)
-        if args.view_metrics:
-            view = res['view']
-            write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
-        if sparsification is not None:
-            write_sparsification(os.path.join(save_path, 'sparsification.txt'), res['sparsification'])
+                                 with_metrics=args.evaluate, device_percentile=args.device_percentile, device_metrics=args.device_metrics,
+                                 disparity=args.disparity, products=products)
+        write_tables(save_path, res)
         with open(os.path.join(save_path, 'errors.txt'), 'w') as f:  # :277-280
             f.write('\nNumber of parameters {}\n'.format(n_params))
             f.write('\nEPE {}\n'.format(res['epe']))
@@ -564,13 +545,12 @@ def main():
         if args.evaluate:  # :282-284
             print('* EPE: {0}'.format(res['epe']))
             print(res['kitti_table'])
-        extra_lines()
+        extra_lines(products)
         print(json.dumps({'dataset': args.tdataName, 'frames': res['n'], 'dtype': args.dtype, 'post': post, 'epe': res['epe'], 'kitti': res['kitti'],
                           'sec_per_image': res['sec_per_image'], 'errors_txt': os.path.join(save_path, 'errors.txt')}))
         return
 
-    if args.pseudo_lidar:
-        lidar_writer, lidar_source = make_lidar_writer()
+    products = make_products()
     left, _, _, _ = synthetic.synthetic_pair(1, args.height, args.width, seed=7)
     left = left.to(dev)
     max_disp = torch.tensor([args.max_disp * args.rel_baselne], device=dev).view(1, 1, 1)  # Test_KITTI.py:181-182
@@ -590,30 +570,19 @@ def main():
                 disp = inference.ms_pp(left, pan_model, disp, min_disp, max_disp, args.device_percentile)
             torch.cuda.synchronize()
             times.append(time.time() - t0)
-        if writer is not None:  # the one seeded frame, after the timed loop
-            inference.dump_frame(writer, 0, pan_model, left, disp, min_disp, max_disp)
-        if sweep_writer is not None:
-            inference.sweep_frame(sweep_writer, 0, pan_model, left, min_disp, max_disp, fractions)
-        if freeview_writer is not None:
-            inference.freeview_frame(freeview_writer, 0, pan_model, left, min_disp, max_disp, fv_poses, fill_beta=args.freeview_fill)
-        if stats_writer is not None:
-            inference.stats_frame(stats_writer, 0, pan_model, left, disp, min_disp, max_disp)
-        if lidar_writer is not None:
-            inference.lidar_frame(lidar_writer, 0, pan_model, left, disp, min_disp, max_disp)
-        if mesh_writer is not None:
-            inference.mesh_frame(mesh_writer, 0, pan_model, left, disp, min_disp, max_disp)
+        # the one seeded frame, after the timed loop.  The timed image is seeded noise and its pair's right image is independent of it: no view
+        # metric means anything there.  The view is judged on a seeded pair with real geometry instead (synthetic.structured_stereo: the right image
+        # IS the left one resampled along a smooth disparity field), at the same size: one more forward on the plan of the timed one
         if args.view_metrics:
-            # the timed image is seeded noise and its pair's right image is independent of it: no view metric means anything there.  The view is
-            # judged on a seeded pair with real geometry instead (synthetic.structured_stereo: the right image IS the left one resampled along a
-            # smooth disparity field), at the same size: one more forward on the plan of the timed one
-            from fal_net_amd import metrics
             s_left, s_right = synthetic.structured_stereo(1, args.height, args.width, seed=7)[:2]
-            view_table = metrics.MetricTable(1, dev)
-            inference.view_frame(view_table, pan_model, s_left.to(dev), s_right.to(dev), min_disp, max_disp)
-            view = inference.view_result(view_table)
-            os.makedirs(save_path, exist_ok=True)
-            write_view_errors(os.path.join(save_path, 'view_errors.txt'), view)
-    extra_lines()
+            inference.run_products([p for p in products if p.key == 'view'],
+                                   inference.Frame(0, pan_model, s_left.to(dev), None, min_disp, max_disp, right=s_right.to(dev)))
+        inference.run_products([p for p in products if p.key != 'view'], inference.Frame(0, pan_model, left, disp, min_disp, max_disp))
+    results = {p.key: p.result() for p in products if hasattr(p, 'result')}
+    if results:
+        os.makedirs(save_path, exist_ok=True)
+    write_tables(save_path, results)
+    extra_lines(products)
     print(json.dumps({'image': [args.height, args.width], 'dtype': args.dtype, 'post': post,
                       'sec_per_image_median': sorted(times)[len(times) // 2], 'disp_mean': float(disp.mean()), 'disp_max': float(disp.max())}))
 

@@ -105,6 +105,13 @@ def filter_point_cloud(img, disp, score, threshold, packed=True, focal=None, bas
     return [o[:c] if packed else o[:, :c] for o, c in zip(outs, kept)], kept
 
 
+def check_min_conf(value, name="min_conf"):
+    """A confidence threshold, or None for no filter; ValueError unless 0 < value <= 1 (a NaN fails both comparisons)."""
+    if value is not None and not 0.0 < value <= 1.0:
+        raise ValueError("{} must lie in (0, 1], got {}".format(name, value))
+    return value
+
+
 class StatsWriter:
     """Test_KITTI.py --stats / --pc-min-conf: writes stats/{frame:010d}_{kind}.png under `save_path` -- std and peak through dumps.disparity_png
     (plasma, p95-normalised), entropy and conf through dumps.feature_u8, arg as the grey rint(255 a / (N - 1)) -- and, with `pc_min_conf`, the
@@ -112,13 +119,13 @@ class StatsWriter:
     Its folder is its own, as dumps.SweepWriter's: FrameWriter and DUMP_KINDS do not know about it.  The means of std, entropy and conf of
     every frame stay on the device until summary()."""
     CLI_KINDS = ("std", "entropy", "arg", "conf", "peak")
+    key = "stats"
 
     def __init__(self, save_path, kinds=(), pc_min_conf=None, ply_format="binary"):
         bad = [k for k in kinds if k not in self.CLI_KINDS]
         if bad:
             raise ValueError("unknown statistic(s) {}: choose from {}".format(", ".join(bad), ", ".join(self.CLI_KINDS)))
-        if pc_min_conf is not None and not 0.0 < pc_min_conf <= 1.0:
-            raise ValueError("pc_min_conf must lie in (0, 1], got {}".format(pc_min_conf))
+        check_min_conf(pc_min_conf, "pc_min_conf")
         self.save_path, self.kinds, self.pc_min_conf, self.ply_format = save_path, tuple(kinds), pc_min_conf, ply_format
         self.folder = os.path.join(save_path, "stats")
         self.pc_folder = os.path.join(save_path, "Point_cloud")
@@ -137,6 +144,13 @@ class StatsWriter:
 
     def file(self, i, kind):
         return os.path.join(self.folder, "{:010d}_{}.png".format(i, kind))
+
+    def frame(self, f):
+        """An inference.Frame: the statistics of the logits of one more disparity-only forward (f.stats); the filtered point cloud is made of
+        `f.disp`, the disparity the run evaluates."""
+        st = f.stats(self.which)
+        B, _, H, W = f.left.shape
+        self.write(f.index, f.left, f.disp, st, f.model._plan(B, H, W, f.left.device).buf["dlog0"].shape[1])
 
     def write(self, i, left, disp, st, n_planes):
         """Frame `i` (batch size 1): left (1, 3, H, W) normalised input, disp (1, 1, H, W) the disparity the cloud is made of, st: stats() with

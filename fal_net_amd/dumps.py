@@ -134,9 +134,17 @@ def point_cloud(img, disp, focal=None, baseline=None, packed=False, mean=MEAN, r
 
 
 # ---- PLY files ---------------------------------------------------------------------------------------------------------------------------
-def _ply_header(fmt, n):
-    return ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
-            "property uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\nend_header\n").format(fmt, n)
+def check_ply_format(ply_format):
+    if ply_format not in ("binary", "ascii"):
+        raise ValueError("ply_format must be 'binary' or 'ascii', got {!r}".format(ply_format))
+
+
+def _ply_header(fmt, n, normals=False, faces=None):
+    """The header of a point cloud; normals: nx ny nz after the coordinates; faces: a count -- the face element of a mesh (mesh.save_ply)."""
+    return ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n{}"
+            "property uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n{}end_header\n").format(
+                fmt, n, "property float nx\nproperty float ny\nproperty float nz\n" if normals else "",
+                "" if faces is None else "element face {}\nproperty list uchar int vertex_indices\n".format(faces))
 
 
 def pack_vertices(pc):
@@ -153,6 +161,7 @@ def save_ply(file_name, planar=None, packed=None, ply_format="binary"):
     """One point cloud to `file_name`.  'ascii': the reference's file (myUtils.py:378-394: '{:f} {:f} {:f} {:d} {:d} {:d}' lines, colours through
     int()) from the planar (6, n) array, formatted a block of vertices at a time; 'binary': binary_little_endian with the same six properties,
     the packed records written as one buffer."""
+    check_ply_format(ply_format)
     if ply_format == "ascii":
         pc = np.asarray(planar)
         n = pc.shape[1]
@@ -165,8 +174,6 @@ def save_ply(file_name, planar=None, packed=None, ply_format="binary"):
                 rows[:, 3:] = pc[3:, s:s + block].T.astype(np.int64)  # int(): truncation toward zero
                 f.write(("%f %f %f %d %d %d\n" * len(rows)) % tuple(rows.ravel()))
         return
-    if ply_format != "binary":
-        raise ValueError("ply_format must be 'binary' or 'ascii', got {!r}".format(ply_format))
     rec = pack_vertices(planar) if packed is None else np.ascontiguousarray(packed).view(np.uint8).reshape(-1, 15)
     with open(file_name, "wb") as f:
         f.write(_ply_header("binary_little_endian", len(rec)).encode("ascii"))
@@ -187,14 +194,14 @@ class FrameWriter:
     file names: l_disp/{:010d}.png, 'Input im'/{:010d}.png, Pan/{:010d}.png, Point_cloud/{:010d}.ply, feats/{:010d}_l{layer}_c{channel}.png.
     `what`: any subset of DUMP_KINDS.  Every image is finished on the device; the host copies bytes and encodes files."""
     folders = {"disp": "l_disp", "input": "Input im", "pan": "Pan", "pc": "Point_cloud", "feats": "feats"}
+    key = "dump"
 
     def __init__(self, save_path, what, ply_format="binary"):
         what = tuple(what)
         bad = [k for k in what if k not in DUMP_KINDS]
         if bad:
             raise ValueError("unknown dump kind(s) {}: choose from {}".format(", ".join(bad), ", ".join(DUMP_KINDS)))
-        if ply_format not in ("binary", "ascii"):
-            raise ValueError("ply_format must be 'binary' or 'ascii', got {!r}".format(ply_format))
+        check_ply_format(ply_format)
         self.save_path, self.what, self.ply_format = save_path, what, ply_format
         self.paths = {k: os.path.join(save_path, d) for k, d in self.folders.items()}
         for p in self.paths.values():  # the reference creates all five, whatever is saved
@@ -209,6 +216,16 @@ class FrameWriter:
         if kind == "feats":
             return os.path.join(self.paths[kind], "{:010d}_l{}_c{}.png".format(i, layer, channel))
         return os.path.join(self.paths[kind], "{:010d}.{}".format(i, "ply" if kind == "pc" else "png"))
+
+    def frame(self, f):
+        """An inference.Frame to disk (Test_KITTI.py:189-194,211-253).  The synthesised view and the occlusion masks come from one more forward with
+        ret_pan / ret_subocc, only where they are wanted; the feature maps are the reference's [local_normalization(input), maskL, maskRL] (its
+        `dispr / 100` is not an output of this model's forward)."""
+        pan = feats = None
+        if self.needs_views:
+            pan, _, mask_l, mask_rl = f.model(f.left, f.min_disp, f.max_disp, ret_disp=True, ret_subocc=True, ret_pan=True)
+            feats = [local_normalization(f.left), mask_l, mask_rl]
+        self.write(f.index, f.left, f.disp, pan=pan, feats=feats)
 
     def write(self, i, left, disp, pan=None, feats=None):
         """Frame `i` (batch size 1, as the reference's loop): left (1, 3, H, W) normalised input, disp (1, 1, H, W), pan: the synthesised view,
@@ -236,11 +253,13 @@ class FrameWriter:
 class SweepWriter:
     """Writes the views of a baseline sweep (fal_net_amd/views.py) under `save_path`: Sweep/{frame:010d}_v{view:02d}.png through image_u8, and
     the disparity in the right view's own frame (the t = 1 view) as r_disp/{frame:010d}.png through disparity_png.  Its two folders are its
-    own: FrameWriter, DUMP_KINDS and the reference's five folders do not know about them."""
+    own: FrameWriter, DUMP_KINDS and the reference's five folders do not know about them.  fractions: the baseline fractions frame() renders;
+    extra: what summary() says besides the file count."""
     folders = {"sweep": "Sweep", "r_disp": "r_disp"}
+    key = "sweep"
 
-    def __init__(self, save_path):
-        self.save_path = save_path
+    def __init__(self, save_path, fractions=(), extra=None):
+        self.save_path, self.fractions, self.extra = save_path, list(fractions), dict(extra or {})
         self.paths = {k: os.path.join(save_path, d) for k, d in self.folders.items()}
         for p in self.paths.values():
             os.makedirs(p, exist_ok=True)
@@ -250,6 +269,19 @@ class SweepWriter:
         if kind == "sweep":
             return os.path.join(self.paths[kind], "{:010d}_v{:02d}.png".format(i, view))
         return os.path.join(self.paths[kind], "{:010d}.png".format(i))
+
+    def frame(self, f):
+        """An inference.Frame's views at self.fractions and the disparity in the right view's own frame (t = 1), all from the logits of one more
+        disparity-only forward (views.render)."""
+        from . import views as V
+        ts = list(self.fractions)
+        if 1.0 not in ts:
+            ts.append(1.0)  # rendered for its disparity only
+        imgs, disps, _ = V.render(f.model, f.left, f.min_disp, f.max_disp, ts)
+        self.write(f.index, imgs[:, :len(self.fractions)], right_disp=disps[:, ts.index(1.0)])
+
+    def summary(self):
+        return dict(self.extra, files=self.files)
 
     def write(self, i, views, right_disp=None):
         """Frame `i` (batch size 1): views (1, V, 3, H, W) normalised images, right_disp (1, 1, H, W) the t = 1 disparity or None."""

@@ -196,11 +196,14 @@ def render(model, left, min_disp, max_disp, poses, want=OUTPUTS, fill=None):
 class FreeviewWriter:
     """Writes free-viewpoint frames under `save_path`: Freeview/{frame:010d}_p{pose:02d}.png through dumps.image_u8 and
     Freeview/{frame:010d}_p{pose:02d}_cover.png through dumps.feature_u8.  The folder is its own: dumps.DUMP_KINDS and dumps.FrameWriter do
-    not know about it.  The mean cover over everything written is kept on the device and read once, by summary()."""
+    not know about it.  The mean cover over everything written is kept on the device and read once, by summary().  poses: the target cameras
+    frame() renders, as pose keyword sets (what `paths` returns); fill_beta: also their hole-filled views (fill_views with that bias) as
+    ..._filled.png; extra: what summary() says besides the counts."""
     folder = "Freeview"
+    key = "freeview"
 
-    def __init__(self, save_path):
-        self.save_path = save_path
+    def __init__(self, save_path, poses=(), fill_beta=None, extra=None):
+        self.save_path, self.poses, self.fill_beta, self.extra = save_path, list(poses), fill_beta, dict(extra or {})
         self.path = os.path.join(save_path, self.folder)
         os.makedirs(self.path, exist_ok=True)
         self.files = 0
@@ -211,6 +214,15 @@ class FreeviewWriter:
 
     def file(self, i, p, cover=False):
         return os.path.join(self.path, "{:010d}_p{:02d}{}.png".format(i, p, "_cover" if cover else ""))
+
+    def frame(self, f):
+        """An inference.Frame's views and cover maps from self.poses around the nominal camera of the frame's size, from the logits of one more
+        disparity-only forward (render)."""
+        K = camera(f.left.shape[-2], f.left.shape[-1])
+        out, _ = render(f.model, f.left, f.min_disp, f.max_disp, [pose(K, **kw) for kw in self.poses], want=("view", "cover"), fill=self.fill_beta)
+        self.write(f.index, out["view"], out["cover"])
+        if self.fill_beta is not None:
+            self.write_filled(f.index, out["view_filled"])
 
     def write(self, i, views, cover):
         """views (1, V, 3, H, W), cover (1, V, 1, H, W) of frame `i`."""
@@ -242,4 +254,4 @@ class FreeviewWriter:
                "mean_cover": float(self._cover_sum) / self._cover_n if self._cover_n else None}
         if self.filled:
             out["filled"] = self.filled
-        return out
+        return dict(out, **self.extra)

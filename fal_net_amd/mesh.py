@@ -15,7 +15,8 @@ import os
 import numpy as np
 import torch
 
-from .dumps import MEAN, PLY_VERTEX
+from .confidence import check_min_conf
+from .dumps import MEAN, PLY_VERTEX, _ply_header, check_ply_format
 
 PLY_VERTEX_NORMALS = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                                ("red", "u1"), ("green", "u1"), ("blue", "u1")])  # 27 bytes, no padding
@@ -81,14 +82,6 @@ def build(img, disp, focal=None, baseline=None, max_jump=0.05, min_depth=0.0, ma
 
 
 # ---- PLY files ---------------------------------------------------------------------------------------------------------------------------------------
-def _ply_header(fmt, nv, nf, normals):
-    """dumps._ply_header's property names, plus nx ny nz, plus the face element."""
-    return ("ply\nformat {} 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n{}"
-            "property uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n"
-            "element face {}\nproperty list uchar int vertex_indices\nend_header\n").format(
-                fmt, nv, "property float nx\nproperty float ny\nproperty float nz\n" if normals else "", nf)
-
-
 def _records(x, width, what):
     a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
@@ -100,13 +93,12 @@ def _records(x, width, what):
 def save_ply(file_name, vertices, faces, normals=False, ply_format="binary"):
     """One mesh to `file_name` from the records build() returns (tensors on any device, or arrays): 'binary' writes binary_little_endian, the two
     record buffers as they are; 'ascii' formats the same records on the host ('%f' coordinates as dumps.save_ply, '3 i j k' faces)."""
-    if ply_format not in ("binary", "ascii"):
-        raise ValueError("ply_format must be 'binary' or 'ascii', got {!r}".format(ply_format))
+    check_ply_format(ply_format)
     vdt = PLY_VERTEX_NORMALS if normals else PLY_VERTEX
     v, f = _records(vertices, vdt.itemsize, "vertices"), _records(faces, PLY_FACE.itemsize, "faces")
     if ply_format == "binary":
         with open(file_name, "wb") as out:
-            out.write(_ply_header("binary_little_endian", len(v), len(f), normals).encode("ascii"))
+            out.write(_ply_header("binary_little_endian", len(v), normals, len(f)).encode("ascii"))
             out.write(v.tobytes())
             out.write(f.tobytes())
         return
@@ -114,7 +106,7 @@ def save_ply(file_name, vertices, faces, normals=False, ply_format="binary"):
     floats = [n for n in vdt.names if vdt[n].kind == "f"]
     line = " ".join(["%f"] * len(floats) + ["%d"] * 3) + "\n"
     with open(file_name, "w") as out:
-        out.write(_ply_header("ascii", len(vr), len(fr), normals))
+        out.write(_ply_header("ascii", len(vr), normals, len(fr)))
         block = 1 << 16
         for s in range(0, len(vr), block):
             part = vr[s:s + block]
@@ -133,13 +125,12 @@ class MeshWriter:
     """Test_KITTI.py --mesh: writes Mesh/{frame:010d}.ply under `save_path`, the frame's depth mesh with the camera of dumps.camera_for_width.  Its
     folder is its own, as dumps.SweepWriter's: FrameWriter and DUMP_KINDS do not know about it.  min_conf: with it, write() needs the frame's
     confidence map and only vertices of conf >= min_conf are valid."""
+    key = "mesh"
 
     def __init__(self, save_path, max_jump=0.05, max_depth=80.0, min_depth=0.0, min_conf=None, normals=False, ply_format="binary"):
         check_depths(float(min_depth), float(max_depth), float(max_jump))
-        if min_conf is not None and not 0.0 < min_conf <= 1.0:
-            raise ValueError("min_conf must lie in (0, 1], got {}".format(min_conf))
-        if ply_format not in ("binary", "ascii"):
-            raise ValueError("ply_format must be 'binary' or 'ascii', got {!r}".format(ply_format))
+        check_min_conf(min_conf)
+        check_ply_format(ply_format)
         self.save_path, self.min_conf, self.normals, self.ply_format = save_path, min_conf, bool(normals), ply_format
         self.kw = dict(max_jump=float(max_jump), max_depth=float(max_depth), min_depth=float(min_depth))
         self.folder = os.path.join(save_path, "Mesh")
@@ -148,6 +139,11 @@ class MeshWriter:
 
     def file(self, i):
         return os.path.join(self.folder, "{:010d}.ply".format(i))
+
+    def frame(self, f):
+        """An inference.Frame: `f.disp`, the disparity the run evaluates, as a mesh; the confidence map (f.conf(): one more disparity-only forward)
+        only when the writer filters by it."""
+        self.write(f.index, f.left, f.disp, conf=f.conf() if self.min_conf is not None else None)
 
     def write(self, i, left, disp, conf=None):
         """Frame `i` (batch size 1): left (1, 3, H, W) normalised input, disp (1, 1, H, W), conf (1, 1, H, W) the confidence map (needed with min_conf)."""

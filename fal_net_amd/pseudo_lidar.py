@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import velodyne
+from .confidence import check_min_conf
 
 MAX_BEAMS, MAX_AZ_BINS = 128, 4096
 
@@ -114,18 +115,19 @@ def write_bin(path, points):
 
 class PseudoLidarWriter:
     """Test_KITTI.py --pseudo-lidar: writes Pseudo_lidar/{frame:010d}.bin under `save_path`, the frame's disparity back-projected with the
-    parameters given here.  calibration: a callable (frame index, H, W) -> (P, fb) -- inference.lidar_frame asks it per frame -- or None when
-    write() is always given both.  min_conf: with it, write() needs the frame's confidence map and keeps only the pixels of conf >= min_conf."""
+    parameters given here.  calibration: a callable (frame index, H, W) -> (P, fb) -- frame() asks it per frame -- or None when
+    write() is always given both.  min_conf: with it, write() needs the frame's confidence map and keeps only the pixels of conf >= min_conf.
+    extra: what summary() says besides the counts."""
+    key = "pseudo_lidar"
 
     def __init__(self, save_path, calibration=None, beams=0, az_bins=1024, max_depth=80.0, max_height=1.0, min_conf=None, min_depth=0.0,
-                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0)):
+                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0), extra=None):
         if beams != 0:
             edge_tables(beams, az_bins, elevation, azimuth)  # the range checks, before the first frame
-        if min_conf is not None and not 0.0 < min_conf <= 1.0:
-            raise ValueError("min_conf must lie in (0, 1], got {}".format(min_conf))
+        check_min_conf(min_conf)
         if not np.isfinite(max_depth) or not max_depth > min_depth:
             raise ValueError("max_depth must be finite and above min_depth, got {}".format(max_depth))
-        self.save_path, self.calibration, self.min_conf = save_path, calibration, min_conf
+        self.save_path, self.calibration, self.min_conf, self.extra = save_path, calibration, min_conf, dict(extra or {})
         self.kw = dict(beams=int(beams), az_bins=int(az_bins), max_depth=float(max_depth), max_height=float(max_height), min_depth=float(min_depth),
                        elevation=tuple(elevation), azimuth=tuple(azimuth))
         self.folder = os.path.join(save_path, "Pseudo_lidar")
@@ -134,6 +136,13 @@ class PseudoLidarWriter:
 
     def file(self, i):
         return os.path.join(self.folder, "{:010d}.bin".format(i))
+
+    def frame(self, f):
+        """An inference.Frame: `f.disp`, the disparity the run evaluates, back-projected with the calibration the writer has for the frame; the
+        confidence map (f.conf(): one more disparity-only forward) only when the writer filters by it."""
+        conf = f.conf() if self.min_conf is not None else None
+        P, fb = self.calibration(f.index, f.disp.shape[-2], f.disp.shape[-1])
+        self.write(f.index, f.disp, P, fb, conf=conf)
 
     def write(self, i, disp, P, fb, conf=None):
         """Frame `i`: disp (1, 1, H, W) or (H, W) disparity on the device, P and fb its calibration, conf the confidence map (needed with min_conf)."""
@@ -155,4 +164,4 @@ class PseudoLidarWriter:
             out["az_bins"] = self.kw["az_bins"]
         if self.min_conf is not None:
             out["min_conf"] = self.min_conf
-        return out
+        return dict(out, **self.extra)

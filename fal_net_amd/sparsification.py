@@ -97,9 +97,11 @@ class SparsificationRow:
 class SparsificationTable:
     """Owns the results table -- (n_frames, row_length) doubles on the device, NaN where nothing was written -- and the workspaces of the kernels
     (grown to the largest frame seen).  `names`: what the scores of every row are called, in order (at most four); `steps`: the cuts S of every curve.  row(i) hands out row i
-    (the table grows on the device when i is beyond it), result() reads everything back ONCE."""
+    (the table grows on the device when i is beyond it), result() reads everything back ONCE.  extra: what summary() says besides the areas."""
+    key = "sparsification"
 
-    def __init__(self, n_frames, names=(), steps=DEFAULT_STEPS, device="cuda"):
+    def __init__(self, n_frames, names=(), steps=DEFAULT_STEPS, device="cuda", extra=None):
+        self.extra = dict(extra or {})
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("fal_net_amd.sparsification runs on an MI355X only (no CPU fallback); asked for " + str(device))
@@ -137,6 +139,21 @@ class SparsificationTable:
         n >= 1, 'ause' / 'aurg': {score: {metric: per-frame array}} over those frames, 'ause_mean' / 'aurg_mean': {score: {metric: float}},
         'curves_mean': {score: {metric: list of S}}, 'oracle_mean': {metric: list of S}}.  No frame with a pixel: the means are NaN."""
         return summarize(self.rows(), self.names, self.steps)
+
+    def frame(self, f):
+        """An inference.Frame with ground truth into the next row; one without is passed over.  The errors are those of `f.disp`, the disparity the
+        run evaluates AFTER post-processing; the scores (self.names, from SCORES) are statistics of the logits of one more disparity-only forward
+        of the plain view (f.stats): with ms_pp or the flip post-processing the scores describe the first of the two blended forwards."""
+        if f.target is None:
+            return
+        st = f.stats(stats_needed(self.names))
+        curves(f.disp, f.target, f.mode, score_maps(st, self.names), use_median=f.use_median, steps=self.steps, out=self.row(self.n))
+
+    def summary(self):
+        """The run's extra JSON line: the mean areas per score (one more read of the table)."""
+        res = self.result()
+        return dict({"scores": res["names"], "steps": res["steps"], "frames": res["frames"], "ause": res["ause_mean"], "aurg": res["aurg_mean"]},
+                    **self.extra)
 
 
 def area(curve):

@@ -161,7 +161,7 @@ class _FixedEval(torch.nn.Module):
 
 
 def test_evaluate_view_metrics():
-    """inference.evaluate(view_metrics=True): the view's errors and SSIM against the loader's right image in a table of their own, read once."""
+    """inference.evaluate(products=[ViewMetrics()]): the view's errors and SSIM against the loader's right image in a table of their own, read once."""
     from fal_net_amd import datasets as DS
     from fal_net_amd import inference
     gen = torch.Generator().manual_seed(6)
@@ -170,7 +170,7 @@ def test_evaluate_view_metrics():
     views = [r + 0.05 * torch.randn(r.shape, generator=gen).to(DEV) for r in rights]
     loader = [[(l, r, None)] for l, r in frames]
     plain = inference.evaluate(_FixedEval(views), loader, post="none", log=None)
-    out = inference.evaluate(_FixedEval(views), loader, post="none", log=None, view_metrics=True)
+    out = inference.evaluate(_FixedEval(views), loader, post="none", log=None, products=[inference.ViewMetrics(len(loader), DEV)])
     assert "view" not in plain and set(out) == set(plain) | {"view"} and out["n"] == plain["n"] == 3
     view = out["view"]
     assert set(view) == {"rmse", "mea", "psnr", "ssim", "n"} and view["n"] == 3

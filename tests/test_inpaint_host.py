@@ -216,10 +216,9 @@ def test_settings_hide_the_argument_when_unused():
     """The filter Test_KITTI.py applies to settings.txt, on parsed arguments: no line for the switch without it, one with it."""
     import Test_KITTI as T
     assert T.FREEVIEW_FILL_ARGS == ("freeview_fill",) and "freeview_fill" not in T.FREEVIEW_ARGS
-    src = open(os.path.join(ROOT, "Test_KITTI.py")).read()
-    assert "hidden += () if args.freeview_fill is not None else FREEVIEW_FILL_ARGS" in src
-    assert "hidden += () if args.freeview is not None else FREEVIEW_ARGS" in src
     off, on = T.parser.parse_args(["--freeview", "2"]), T.parser.parse_args(["--freeview", "2", "--freeview-fill"])
+    assert set(T.FREEVIEW_FILL_ARGS) <= set(T.hidden_settings(off)) and not set(T.FREEVIEW_FILL_ARGS) & set(T.hidden_settings(on))
+    assert not set(T.FREEVIEW_ARGS) & set(T.hidden_settings(off)) and set(T.FREEVIEW_ARGS) <= set(T.hidden_settings(T.parser.parse_args([])))
     assert set(vars(on)) - set(T.FREEVIEW_FILL_ARGS) == set(vars(off)) - set(T.FREEVIEW_FILL_ARGS)
 
 

@@ -125,27 +125,27 @@ def test_parser_and_what_settings_hide(monkeypatch):
     mod = importlib.import_module("Test_KITTI")
     a = mod.parser.parse_args([])
     assert (a.mesh, a.mesh_max_jump, a.mesh_max_depth, a.mesh_min_conf, a.mesh_normals) == (False, 0.05, 80.0, None, False)
-    mod.check_mesh_args(a)
+    mod.check_family_args(a)
     assert mod.MESH_ARGS == ("mesh", "mesh_max_jump", "mesh_max_depth", "mesh_min_conf", "mesh_normals") and set(mod.MESH_ARGS) <= set(vars(a))
-    src = open(os.path.join(ROOT, "Test_KITTI.py")).read()
-    assert re.search(r"hidden \+= \(\) if args\.mesh else MESH_ARGS", src)  # settings.txt keeps its lines without --mesh
+    assert set(mod.MESH_ARGS) <= set(mod.hidden_settings(a))  # settings.txt keeps its lines without --mesh
+    assert not set(mod.MESH_ARGS) & set(mod.hidden_settings(mod.parser.parse_args(["--mesh"])))
     a = mod.parser.parse_args(["--mesh", "--mesh-max-jump", "inf", "--mesh-max-depth", "60", "--mesh-min-conf", "0.5", "--mesh-normals"])
     assert (a.mesh, a.mesh_max_jump, a.mesh_max_depth, a.mesh_min_conf, a.mesh_normals) == (True, float("inf"), 60.0, 0.5, True)
-    mod.check_mesh_args(a)
+    mod.check_family_args(a)
     for bad in (["--mesh-max-jump", "-0.1"], ["--mesh-max-jump", "nan"], ["--mesh-max-depth", "200"], ["--mesh-max-depth", "0"], ["--mesh-max-depth", "nan"],
                 ["--mesh-min-conf", "0"], ["--mesh-min-conf", "1.5"]):
         with pytest.raises(SystemExit):
             mod.parser.parse_args(["--mesh"] + bad)
     for alone in (["--mesh-max-jump", "0.1"], ["--mesh-max-depth", "60"], ["--mesh-min-conf", "0.5"], ["--mesh-normals"]):
         with pytest.raises(SystemExit, match="--mesh"):
-            mod.check_mesh_args(mod.parser.parse_args(alone))
+            mod.check_family_args(mod.parser.parse_args(alone))
         with pytest.raises(SystemExit, match=alone[0]):
-            mod.check_mesh_args(mod.parser.parse_args(alone))
-    mod.check_lidar_args(mod.parser.parse_args(["--mesh"]))  # and the other families' checks do not see it
+            mod.check_family_args(mod.parser.parse_args(alone))
+    mod.check_family_args(mod.parser.parse_args(["--mesh"]))  # and the other families' checks do not see it
 
 
 def test_entry_points_in_header_binding_and_build():
-    from fal_net_amd import _build, _lib, inference, ops
+    from fal_net_amd import _build, _lib, inference, mesh, ops
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "falnet_hip.h")).read(), flags=re.S)
     assert re.search(r"\bfalnet_mesh_build\s*\(", hdr) and re.search(r"\bfalnet_mesh_workspace_bytes\s*\(", hdr)
     P, F, D, I = _lib._P, _lib._F, _lib._D, _lib._I
@@ -158,7 +158,7 @@ def test_entry_points_in_header_binding_and_build():
     # the vertex chain is written once: in the header both files include
     dump = open(os.path.join(_build.CSRC, "dump.hip")).read()
     assert '#include "pc_vertex.h"' in src and '#include "pc_vertex.h"' in dump and "PcVertex pc_vertex(" not in dump and "PcVertex pc_vertex(" not in src
-    assert callable(inference.mesh_frame)
+    assert callable(mesh.MeshWriter.frame) and callable(inference.run_products)
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "fal_net_amd", "libfalnet_hip.so")), reason="library not built")

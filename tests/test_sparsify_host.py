@@ -159,8 +159,8 @@ def test_parser_refusals_and_what_settings_hide(monkeypatch):
     mod.check_sparsification_args(a, False)
     assert set(mod.SPARSIFICATION_ARGS) == {"sparsification", "sparsification_steps"} <= set(vars(a))
     assert tuple(mod.SPARSIFICATION_SCORES) == tuple(SP.SCORES)
-    src = open(os.path.join(ROOT, "Test_KITTI.py")).read()
-    assert re.search(r"hidden \+= \(\) if args\.sparsification is not None else SPARSIFICATION_ARGS", src)  # settings.txt keeps its lines without the switch
+    assert set(mod.SPARSIFICATION_ARGS) <= set(mod.hidden_settings(a))  # settings.txt keeps its lines without the switch
+    assert not set(mod.SPARSIFICATION_ARGS) & set(mod.hidden_settings(mod.parser.parse_args(["--sparsification", "std"])))
     a = mod.parser.parse_args(["--sparsification", "std,entropy,conf,relstd", "--sparsification-steps", "20"])
     assert a.sparsification == ["std", "entropy", "conf", "relstd"] and a.sparsification_steps == 20
     mod.check_sparsification_args(a, True)
@@ -169,7 +169,7 @@ def test_parser_refusals_and_what_settings_hide(monkeypatch):
     with pytest.raises(SystemExit, match="-eval True"):
         mod.check_sparsification_args(mod.parser.parse_args(["--sparsification", "std", "-eval", "False"]), True)
     with pytest.raises(SystemExit, match="add --sparsification"):
-        mod.check_sparsification_args(mod.parser.parse_args(["--sparsification-steps", "20"]), True)
+        mod.check_family_args(mod.parser.parse_args(["--sparsification-steps", "20"]))
     for bad in (["--sparsification", "peak"], ["--sparsification", "std,std"], ["--sparsification", ""], ["--sparsification", "std", "--sparsification-steps", "1"],
                 ["--sparsification", "std", "--sparsification-steps", "101"]):
         with pytest.raises(SystemExit):

@@ -118,7 +118,7 @@ def test_steps_and_loops_take_the_switches_off_by_default():
     for f in (train.stage1_step, train.stage1_slow_step):
         assert inspect.signature(f).parameters["a_ssim"].default == 0.0
     assert "a_ssim" not in inspect.signature(train.stage2_step).parameters
-    assert inspect.signature(inference.evaluate).parameters["view_metrics"].default is False
+    assert inspect.signature(inference.evaluate).parameters["products"].default == ()
 
 
 def test_new_switches_parse(monkeypatch):
@@ -137,7 +137,8 @@ def test_new_switches_parse(monkeypatch):
     assert te.parser.parse_args([]).view_metrics is False
     a = te.parser.parse_args(["--view-metrics", "--synthetic", "--device-metrics"])
     assert a.view_metrics is True and a.synthetic and a.device_metrics
-    assert "view_metrics=args.view_metrics" in open(os.path.join(ROOT, "Test_KITTI.py")).read()
+    src = open(os.path.join(ROOT, "Test_KITTI.py")).read()
+    assert re.search(r"if args\.view_metrics:\s+products\.append\(inference\.ViewMetrics\(", src)  # the switch is what puts the product into the run
 
 
 def test_stage2_refuses_the_ssim_term():
