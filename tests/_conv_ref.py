@@ -213,6 +213,14 @@ def unit_roundoff(out_dtype):
     return {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -21}[out_dtype]
 
 
+def violations(got, ref, mag, out_dtype, mag_coef=1e-5):
+    """Boolean tensor in the output layout: the mapped elements compare() counts as `bad` (where a fault shows, not only how often)."""
+    mapped = ~torch.isnan(ref)
+    r, m = torch.nan_to_num(ref), torch.nan_to_num(mag)
+    ok = (got.to(torch.float64) - r).abs() <= unit_roundoff(out_dtype) * r.abs() + mag_coef * m  # a NaN in `got` fails here
+    return mapped & ~ok
+
+
 def compare(got, ref, mag, out_dtype, mag_coef=1e-5):
     """Element-wise check of a launch's output against conv_ref: mapped elements (ref not NaN) within u |ref| + mag_coef mag, unmapped
     ones still NaN (the sentinel the caller filled the buffer with).  Returns dict(bad, unmapped_written, worst_ratio, maxnorm_rel)."""
