@@ -63,7 +63,7 @@ def build_ab(tag="ab", defines=(), verbose=True, raw=()):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "ordered.h"), os.path.join(CSRC, "depth_pair.h"), os.path.join(CSRC, "med_planes.h"), os.path.join(CSRC, "pc_vertex.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "ordered.h"), os.path.join(CSRC, "depth_pair.h"), os.path.join(CSRC, "med_planes.h"), os.path.join(CSRC, "pc_vertex.h"), os.path.join(CSRC, "wgrad_dispatch.h"), os.path.join(HERE, "..", "include", "falnet_hip.h")]
     jobs = []
     for src in SOURCES:
         path = os.path.join(CSRC, src)

@@ -15,6 +15,8 @@ F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 OUT_NHWC, OUT_PLANAR_F32 = 0, 1
 CPAD = 32  # channel padding granule of NHWC tensors / packed weights (falnet_channel_pad)
+# kernel ids falnet_wgrad_kernel_name returns (include/falnet_hip.h: FALNET_WGK_*)
+WGK_TAP, WGK_PATCH, WGK_S2, WGK_C3, WGK_C3WAVE, WGK_ROWS, WGK_ROWS_S2, WGK_WAVE = range(8)
 
 # FALNET_DETERMINISTIC=1: bit-identical results from run to run (include/falnet_hip.h: falnet_set_deterministic; host side in ops.py)
 DETERMINISTIC = os.environ.get("FALNET_DETERMINISTIC") == "1"
@@ -122,6 +124,7 @@ SIGNATURES = {
     "falnet_wgrad_workspace_bytes": [C.POINTER(Wgrad)],
     "falnet_wgrad": [C.POINTER(Wgrad), _P],
     "falnet_wgrad_fuses_bias": [C.POINTER(Wgrad)],
+    "falnet_wgrad_kernel_name": [C.POINTER(Wgrad), C.c_char_p, _I],
     "falnet_wgrad_reduce": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P],
     "falnet_bias_grad": [_P, _L, _I, _I, _P, _I, _I, _P],
     "falnet_pack_weights_batched": [_P, _I, _I, _I, _P],

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "conv_epilogue.h"  // f32x16
+#include "wgrad_dispatch.h"
 
 #define CONV_THREADS 256  // threads of wgrad_kernel's workgroup
 
@@ -1033,64 +1034,60 @@ extern "C" int64_t falnet_wgrad_workspace_bytes(const falnet_wgrad_t* p) {
 // A/B switch for tests and profiling (conv.hip reads the same variable): FALNET_DISABLE_PATCH=1 routes dense 3x3 launches to the per-tap kernel
 static bool g_disable_patch = [] { const char* e = falnet_ab_env("FALNET_DISABLE_PATCH"); return e && e[0] == '1'; }();
 
-// kernel selection of falnet_wgrad -- ONE place, also behind falnet_wgrad_fuses_bias (the host must not re-derive it)
-enum WgradKernel { WGK_BAD = -1, WGK_TAP = 0, WGK_PATCH11, WGK_PATCH12, WGK_PATCH21, WGK_S2, WGK_C3, WGK_ROWS, WGK_ROWS_S2, WGK_WAVE };
-bool falnet_wgrad_rows_applicable(const falnet_wgrad_t& p);           // wgrad_rows.hip
-int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_rows_s2_applicable(const falnet_wgrad_t& p);        // wgrad_rows.hip: row-streaming form of the stride-2 weight gradient (variant 8)
-int falnet_wgrad_rows_s2_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_wave_applicable(const falnet_wgrad_t& p);           // wgrad_wave.hip: wave-streaming kernel for 32-channel inputs (variant 9)
-int falnet_wgrad_wave_launch(const falnet_wgrad_t& p, hipStream_t st);
-bool falnet_wgrad_c3wave_applicable(const falnet_wgrad_t& p);         // wgrad_wave.hip: the first layer's gradient in the wave-streaming form (variant 6, IW % 4 == 0)
-int falnet_wgrad_c3wave_launch(const falnet_wgrad_t& p, hipStream_t st);
-
-static bool canonical_taps9(const falnet_wgrad_t& p) {
-    if (p.ntaps != 9) return false;
-    for (int t = 0; t < 9; ++t)
-        if (p.tap_dy[t] != t / 3 - 1 || p.tap_dx[t] != t % 3 - 1) return false;
-    return true;
-}
-
-// returns the kernel; on WGK_BAD the error text is set
-static WgradKernel choose_wgrad_kernel(const falnet_wgrad_t& p) {
+// kernel selection of falnet_wgrad -- ONE place (choose_wgrad_kernel), also behind falnet_wgrad_fuses_bias and falnet_wgrad_kernel_name: the
+// host asks and re-derives nothing.  On WGK_BAD the error text is set.
+static WgradChoice choose_wgrad_kernel(const falnet_wgrad_t& p) {
+    WgradChoice c;
     const int w_rows = round32(p.gC);
     const bool h16 = p.dtype == FALNET_BF16 || p.dtype == FALNET_F16;
-    const bool canon = canonical_taps9(p);
-    if (p.up2 && p.variant != 7) { falnet_set_error("wgrad: up2 (a deconv layer's gradient on the low-resolution grid) is a mode of variant 7 only"); return WGK_BAD; }
+    const bool canon = falnet_wgrad_canonical_taps9(p);
+    if (p.up2 && p.variant != 7) { falnet_set_error("wgrad: up2 (a deconv layer's gradient on the low-resolution grid) is a mode of variant 7 only"); return c; }
     if (p.variant == 6) {  // first layer: planar f32 3-channel source (src[0].ptr = [B][3][IH][IW] f32), 16-bit gout, Cout 32
         const bool ok = h16 && canon && p.isy == 1 && p.isx == 1 && p.TH == p.IH && p.TW == p.IW && p.gC == 32 && w_rows == 32 && p.cin_total == 32 && p.nsrc == 1;
-        if (!ok) { falnet_set_error("wgrad: variant 6 is the Cin=3 / Cout=32 first layer in bf16 / f16 (dense 3x3, cin_total 32)"); return WGK_BAD; }
-        return WGK_C3;
+        if (!ok) { falnet_set_error("wgrad: variant 6 is the Cin=3 / Cout=32 first layer in bf16 / f16 (dense 3x3, cin_total 32)"); return c; }
+        c.kernel = falnet_wgrad_c3wave_applicable(p) ? WGK_C3WAVE : WGK_C3;  // the wave-streaming form where it applies, else the halo-patch form
+        return c;
     }
     if (p.variant == 5) {  // stride-2 3x3 (16-bit): parity-plane halo kernel
         bool ok = h16 && canon && p.isy == 2 && p.isx == 2 && p.TW >= 16 && p.TH == (p.IH + 1) / 2 && p.TW == (p.IW + 1) / 2;
         for (int s = 0; s < p.nsrc && ok; ++s) ok = p.src[s].C % 32 == 0 && ((p.src[s].H == p.IH && p.src[s].W == p.IW) || (p.src[s].sy == 0 && p.src[s].sx == 0));
-        if (!ok) { falnet_set_error("wgrad: variant 5 needs a 16-bit 3x3 stride-2 pad-1 launch with sources at the input size"); return WGK_BAD; }
-        return WGK_S2;
+        if (!ok) { falnet_set_error("wgrad: variant 5 needs a 16-bit 3x3 stride-2 pad-1 launch with sources at the input size"); return c; }
+        c.kernel = WGK_S2;
+        c.cow = w_rows % 64 == 0 ? 2 : 1;
+        return c;
     }
     if (p.variant == 8) {
-        if (!falnet_wgrad_rows_s2_applicable(p)) { falnet_set_error("wgrad: variant 8 needs a 16-bit 3x3 stride-2 pad-1 launch with ONE source at the input size"); return WGK_BAD; }
-        return WGK_ROWS_S2;
+        if (!falnet_wgrad_rows_s2_applicable(p)) { falnet_set_error("wgrad: variant 8 needs a 16-bit 3x3 stride-2 pad-1 launch with ONE source at the input size"); return c; }
+        c.kernel = WGK_ROWS_S2;
+        return c;
     }
     if (p.variant == 9) {
-        if (!falnet_wgrad_wave_applicable(p)) { falnet_set_error("wgrad: variant 9 needs a 16-bit dense 3x3 stride-1 launch over ONE 32-channel NHWC source at the launch size, gC 32 or 64, TW >= 32"); return WGK_BAD; }
-        return WGK_WAVE;
+        if (!falnet_wgrad_wave_applicable(p)) { falnet_set_error("wgrad: variant 9 needs a 16-bit dense 3x3 stride-1 launch over ONE 32-channel NHWC source at the launch size, gC 32 or 64, TW >= 32"); return c; }
+        c.kernel = WGK_WAVE;
+        c.s2 = p.isy == 2;
+        c.nco = c.s2 || p.gC == 64 ? 2 : 1;
+        return c;
     }
     if (p.variant == 7) {
-        if (!falnet_wgrad_rows_applicable(p)) { falnet_set_error("wgrad: variant 7 needs a 16-bit dense 3x3 stride-1 launch with sources at the launch size or half of it (up2: ONE source at the launch size; up2 = 1: nsplit a multiple of 4)"); return WGK_BAD; }
-        return WGK_ROWS;
+        if (!falnet_wgrad_rows_applicable(p)) { falnet_set_error("wgrad: variant 7 needs a 16-bit dense 3x3 stride-1 launch with sources at the launch size or half of it (up2: ONE source at the launch size; up2 = 1: nsplit a multiple of 4)"); return c; }
+        c.kernel = WGK_ROWS;
+        c.up2 = p.up2 == 2 ? 2 : p.up2 ? 1 : 0;
+        return c;
     }
     // dense 3x3 stride-1 -> halo-patch kernel (one slab per workgroup; nsplit = pixel-range splits)
     const bool dense = canon && p.isy == 1 && p.isx == 1 && p.TH == p.IH && p.TW == p.IW && p.TW >= 16 && !g_disable_patch && p.variant != 1;
     if (dense) {
         if (p.variant == 3 || p.variant == 4) {  // 32 x 64 / 64 x 32 channels per workgroup (register staged, two workgroups per CU)
             const bool co2 = p.variant == 3;
-            if (!(h16 && (co2 ? w_rows : p.cin_total) % 64 == 0)) { falnet_set_error("wgrad: variant %d needs 16-bit operands and a channel count that is a multiple of 64", p.variant); return WGK_BAD; }
-            return co2 ? WGK_PATCH12 : WGK_PATCH21;
+            if (!(h16 && (co2 ? w_rows : p.cin_total) % 64 == 0)) { falnet_set_error("wgrad: variant %d needs 16-bit operands and a channel count that is a multiple of 64", p.variant); return c; }
+            c.ciw = co2 ? 1 : 2;
+            c.cow = co2 ? 2 : 1;
         }
-        return WGK_PATCH11;
+        c.kernel = WGK_PATCH;
+        return c;
     }
-    return WGK_TAP;
+    c.kernel = WGK_TAP;
+    return c;
 }
 
 static int check_wgrad_desc(const falnet_wgrad_t& p) {
@@ -1112,14 +1109,115 @@ static int check_wgrad_desc(const falnet_wgrad_t& p) {
     return 0;
 }
 
-static bool wgrad_kernel_fuses_bias(WgradKernel k) {
-    if (falnet_deterministic()) return false;  // the fused form adds with f32 atomics from every workgroup
-    return k == WGK_PATCH11 || k == WGK_PATCH12 || k == WGK_PATCH21 || k == WGK_S2 || k == WGK_C3 || k == WGK_ROWS || k == WGK_ROWS_S2 || k == WGK_WAVE;
+// the halo kernels of this file cut the launch into 4 x 32 patches, `pps` of them per split
+struct PatchGrid {
+    int w_rows, tiles_x, tiles_y, pps;
+    explicit PatchGrid(const falnet_wgrad_t& p) : w_rows(round32(p.gC)), tiles_x((p.TW + WP_TW - 1) / WP_TW), tiles_y((p.TH + WP_TH - 1) / WP_TH) {
+        pps = (p.B * tiles_x * tiles_y + p.nsplit - 1) / p.nsplit;
+    }
+};
+
+static int launch_tap(const falnet_wgrad_t& p, const WgradChoice&, hipStream_t st) {
+    const int w_rows = round32(p.gC);
+    const dim3 grid((p.cin_total + WG_BN - 1) / WG_BN, (w_rows + WG_BM - 1) / WG_BM, p.ntaps * p.nsplit);
+#define WG_TAP(T) hipLaunchKernelGGL(wgrad_kernel<T>, grid, dim3(CONV_THREADS), 0, st, p, w_rows)
+    FALNET_DISPATCH_DTYPE(p.dtype, WG_TAP);
+#undef WG_TAP
+    return 0;
+}
+
+static int launch_patch(const falnet_wgrad_t& p, const WgradChoice& c, hipStream_t st) {
+    const PatchGrid g(p);
+#define WG_P(T, CI, CO) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, CI, CO>), dim3(p.cin_total / (32 * CI), g.w_rows / (32 * CO), p.nsplit), dim3(WP_THREADS), 0, st, p, g.w_rows, g.tiles_x, g.tiles_y, g.pps)
+#define WG_P12(T) WG_P(T, 1, 2)
+#define WG_P21(T) WG_P(T, 2, 1)
+#define WG_P11(T) WG_P(T, 1, 1)
+    if (c.cow == 2) FALNET_DISPATCH_16(p.dtype, WG_P12);
+    else if (c.ciw == 2) FALNET_DISPATCH_16(p.dtype, WG_P21);
+    else FALNET_DISPATCH_DTYPE(p.dtype, WG_P11);
+#undef WG_P11
+#undef WG_P21
+#undef WG_P12
+#undef WG_P
+    return 0;
+}
+
+static int launch_s2(const falnet_wgrad_t& p, const WgradChoice& c, hipStream_t st) {
+    const PatchGrid g(p);
+#define WG_S2(T, CO) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_s2_kernel<T, CO>), dim3(p.cin_total / 32, g.w_rows / (32 * CO), p.nsplit), dim3(WP_THREADS), 0, st, p, g.w_rows, g.tiles_x, g.tiles_y, g.pps)
+#define WG_S2_2(T) WG_S2(T, 2)
+#define WG_S2_1(T) WG_S2(T, 1)
+    if (c.cow == 2) FALNET_DISPATCH_16(p.dtype, WG_S2_2);
+    else FALNET_DISPATCH_16(p.dtype, WG_S2_1);
+#undef WG_S2_1
+#undef WG_S2_2
+#undef WG_S2
+    return 0;
+}
+
+static int launch_c3(const falnet_wgrad_t& p, const WgradChoice&, hipStream_t st) {
+    const PatchGrid g(p);
+#define WG_C3(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_c3_kernel<T>), dim3(1, 1, p.nsplit), dim3(WC3_THREADS), 0, st, p, g.w_rows, g.tiles_x, g.tiles_y, g.pps)
+    FALNET_DISPATCH_16(p.dtype, WG_C3);
+#undef WG_C3
+    return 0;
+}
+
+// One row per kernel: the symbol of the instantiation a choice selects (t = the mangled operand type), the function that launches it and
+// whether it sums the bias gradient.  falnet_wgrad, falnet_wgrad_fuses_bias and falnet_wgrad_kernel_name all go through this table, so the
+// reported symbol cannot drift from the kernel launched; a new kernel is one enum member (wgrad_dispatch.h), one branch of
+// choose_wgrad_kernel and one row here.
+struct WgradKernelRow {
+    WgradKernel kernel;
+    int (*symbol)(char* buf, int len, const char* t, const WgradChoice& c);
+    int (*launch)(const falnet_wgrad_t& p, const WgradChoice& c, hipStream_t st);
+    bool fuses_bias;  // (never in deterministic mode: the fused form adds with f32 atomics from every workgroup)
+};
+#define SYMBOL(...) [](char* buf, int len, const char* t, const WgradChoice& c) { (void)c; return snprintf(buf, len, __VA_ARGS__); }
+static const WgradKernelRow wgrad_kernels[] = {
+    {WGK_TAP, SYMBOL("_Z12wgrad_kernelI%sEv14falnet_wgrad_ti", t), launch_tap, false},
+    {WGK_PATCH, SYMBOL("_Z21wgrad3x3_patch_kernelI%sLi%dELi%dEEv14falnet_wgrad_tiiii", t, c.ciw, c.cow), launch_patch, true},
+    {WGK_S2, SYMBOL("_Z18wgrad3x3_s2_kernelI%sLi%dEEv14falnet_wgrad_tiiii", t, c.cow), launch_s2, true},
+    {WGK_C3, SYMBOL("_Z18wgrad3x3_c3_kernelI%sEv14falnet_wgrad_tiiii", t), launch_c3, true},
+    {WGK_C3WAVE, SYMBOL("_Z22wgrad3x3_c3wave_kernelI%sEv14falnet_wgrad_ti", t), falnet_wgrad_c3wave_launch, true},
+    {WGK_ROWS, [](char* buf, int len, const char* t, const WgradChoice& c) {
+         if (c.up2 == 2) return snprintf(buf, len, "_Z20wgrad3x3_up2q_kernelI%sLi2EEv14falnet_wgrad_tiiii", t);
+         return snprintf(buf, len, "_Z22wgrad3x3_rows16_kernelI%sLi4ELi2ELb%dEEv14falnet_wgrad_tiiii", t, c.up2 == 1 ? 1 : 0);
+     },
+     falnet_wgrad_rows_launch, true},
+    {WGK_ROWS_S2, SYMBOL("_Z23wgrad3x3_rows8s2_kernelI%sLi2EEv14falnet_wgrad_tiiii", t), falnet_wgrad_rows_s2_launch, true},
+    {WGK_WAVE, SYMBOL("_Z22wgrad3x3_wave32_kernelI%sLi%dELb%dEEv14falnet_wgrad_ti", t, c.nco, c.s2 ? 1 : 0), falnet_wgrad_wave_launch, true},
+};
+#undef SYMBOL
+
+// the choice for a checked descriptor and its row; nullptr with the error text set when the descriptor is refused
+static const WgradKernelRow* wgrad_kernel_row(const falnet_wgrad_t& p, WgradChoice& c) {
+    c = choose_wgrad_kernel(p);
+    if (c.kernel == WGK_BAD) return nullptr;
+    for (const WgradKernelRow& r : wgrad_kernels)
+        if (r.kernel == c.kernel) return &r;
+    falnet_set_error("wgrad: kernel %d has no table row", (int)c.kernel);
+    return nullptr;
 }
 
 extern "C" int falnet_wgrad_fuses_bias(const falnet_wgrad_t* pp) {
-    if (!pp || check_wgrad_desc(*pp) != 0) return 0;
-    return wgrad_kernel_fuses_bias(choose_wgrad_kernel(*pp)) ? 1 : 0;
+    WgradChoice c;
+    const WgradKernelRow* row = pp && check_wgrad_desc(*pp) == 0 ? wgrad_kernel_row(*pp, c) : nullptr;
+    return row && row->fuses_bias && !falnet_deterministic() ? 1 : 0;
+}
+
+// Id (FALNET_WGK_*) and symbol of the kernel falnet_wgrad will launch for this descriptor (the name rocprofv3 reports): the same checks and
+// the same choice, nothing issued, no pointer dereferenced, no workspace needed.
+extern "C" int falnet_wgrad_kernel_name(const falnet_wgrad_t* pp, char* buf, int len) {
+    FALNET_CHECK_ARG(pp && buf && len > 0, "wgrad_kernel_name: bad argument");
+    if (check_wgrad_desc(*pp) != 0) return -1;
+    WgradChoice c;
+    const WgradKernelRow* row = wgrad_kernel_row(*pp, c);
+    if (!row) return -1;
+    row->symbol(buf, len, pp->dtype == FALNET_BF16 ? "DF16b" : pp->dtype == FALNET_F16 ? "DF16_" : "f", c);
+    return (int)c.kernel;
 }
 
 extern "C" int falnet_wgrad(const falnet_wgrad_t* pp, void* stream) {
@@ -1129,53 +1227,14 @@ extern "C" int falnet_wgrad(const falnet_wgrad_t* pp, void* stream) {
     if (int r = check_wgrad_desc(p)) return r;
     FALNET_CHECK_ARG(p.partial, "wgrad: no workspace");
     if (p.cout == 0) p.cout = p.gC;
-    const int w_rows = round32(p.gC);
-    const WgradKernel k = choose_wgrad_kernel(p);
-    if (k == WGK_BAD) return -1;
-    if (p.bias_grad && !wgrad_kernel_fuses_bias(k)) {
-        falnet_set_error("wgrad: bias_grad is set but the selected kernel (%d) cannot fuse it -- ask falnet_wgrad_fuses_bias first", (int)k);
+    WgradChoice c;
+    const WgradKernelRow* row = wgrad_kernel_row(p, c);
+    if (!row) return -1;
+    if (p.bias_grad && !(row->fuses_bias && !falnet_deterministic())) {
+        falnet_set_error("wgrad: bias_grad is set but the selected kernel (%d) cannot fuse it -- ask falnet_wgrad_fuses_bias first", (int)c.kernel);
         return -3;
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles_x = (p.TW + WP_TW - 1) / WP_TW, tiles_y = (p.TH + WP_TH - 1) / WP_TH;
-    const int npatch = p.B * tiles_x * tiles_y;
-    const int pps = (npatch + p.nsplit - 1) / p.nsplit;
-    switch (k) {
-    case WGK_ROWS:
-        return falnet_wgrad_rows_launch(p, st);
-    case WGK_ROWS_S2:
-        return falnet_wgrad_rows_s2_launch(p, st);
-    case WGK_WAVE:
-        return falnet_wgrad_wave_launch(p, st);
-    case WGK_C3:
-        if (falnet_wgrad_c3wave_applicable(p)) return falnet_wgrad_c3wave_launch(p, st);
-#define WG_C3(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_c3_kernel<T>), dim3(1, 1, p.nsplit), dim3(WC3_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_C3);
-        break;
-    case WGK_S2:
-#define WG_S2_2(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_s2_kernel<T, 2>), dim3(p.cin_total / 32, w_rows / 64, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-#define WG_S2_1(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_s2_kernel<T, 1>), dim3(p.cin_total / 32, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        if (w_rows % 64 == 0) FALNET_DISPATCH_16(p.dtype, WG_S2_2);
-        else FALNET_DISPATCH_16(p.dtype, WG_S2_1);
-        break;
-    case WGK_PATCH12:
-#define WG_P12(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 1, 2>), dim3(p.cin_total / 32, w_rows / 64, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_P12);
-        break;
-    case WGK_PATCH21:
-#define WG_P21(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 2, 1>), dim3(p.cin_total / 64, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_16(p.dtype, WG_P21);
-        break;
-    case WGK_PATCH11:
-#define WG_P11(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_patch_kernel<T, 1, 1>), dim3(p.cin_total / 32, w_rows / 32, p.nsplit), dim3(WP_THREADS), 0, st, p, w_rows, tiles_x, tiles_y, pps)
-        FALNET_DISPATCH_DTYPE(p.dtype, WG_P11);
-        break;
-    default: {
-        const dim3 grid((p.cin_total + WG_BN - 1) / WG_BN, (w_rows + WG_BM - 1) / WG_BM, p.ntaps * p.nsplit);
-#define WG_TAP(T) hipLaunchKernelGGL(wgrad_kernel<T>, grid, dim3(CONV_THREADS), 0, st, p, w_rows)
-        FALNET_DISPATCH_DTYPE(p.dtype, WG_TAP);
-    }
-    }
+    if (int r = row->launch(p, c, (hipStream_t)stream)) return r;
     FALNET_RETURN_LAUNCH();
 }
 

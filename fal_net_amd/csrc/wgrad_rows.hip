@@ -24,6 +24,7 @@
 // the channel tiles of one pixel range on one XCD (they stream the same rows: L2 hits).
 #include <stdlib.h>
 #include "common.h"
+#include "wgrad_dispatch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1614,9 +1615,7 @@ __global__ __launch_bounds__(WR8_THREADS, 2) void wgrad3x3_rows8s2_kernel(const 
 
 bool falnet_wgrad_rows_s2_applicable(const falnet_wgrad_t& p) {
     if (p.dtype != FALNET_BF16 && p.dtype != FALNET_F16) return false;
-    if (p.ntaps != 9 || p.isy != 2 || p.isx != 2 || p.TH != (p.IH + 1) / 2 || p.TW != (p.IW + 1) / 2) return false;
-    for (int t = 0; t < 9; ++t)
-        if (p.tap_dy[t] != t / 3 - 1 || p.tap_dx[t] != t % 3 - 1) return false;
+    if (!falnet_wgrad_canonical_taps9(p) || p.isy != 2 || p.isx != 2 || p.TH != (p.IH + 1) / 2 || p.TW != (p.IW + 1) / 2) return false;
     if (p.gC % 32 || p.cin_total % 32 || p.nsrc != 1) return false;
     const falnet_src_t& S = p.src[0];
     if (S.C != p.cin_total || S.H != p.IH || S.W != p.IW || S.sx == 0 || S.sy == 0) return false;
@@ -1624,7 +1623,7 @@ bool falnet_wgrad_rows_s2_applicable(const falnet_wgrad_t& p) {
     return true;
 }
 
-int falnet_wgrad_rows_s2_launch(const falnet_wgrad_t& p, hipStream_t st) {
+int falnet_wgrad_rows_s2_launch(const falnet_wgrad_t& p, const WgradChoice&, hipStream_t st) {
     const int w_rows = (p.gC + 31) / 32 * 32;
     const int ntci = (p.cin_total + 63) / 64, ntco = (w_rows + 63) / 64;
     const int ntiles = ntci * ntco;
@@ -1639,9 +1638,7 @@ int falnet_wgrad_rows_s2_launch(const falnet_wgrad_t& p, hipStream_t st) {
 // size or exactly half of it, at least one 64-channel side)
 bool falnet_wgrad_rows_applicable(const falnet_wgrad_t& p) {
     if (p.dtype != FALNET_BF16 && p.dtype != FALNET_F16) return false;
-    if (p.ntaps != 9 || p.isy != 1 || p.isx != 1 || p.TH != p.IH || p.TW != p.IW) return false;
-    for (int t = 0; t < 9; ++t)
-        if (p.tap_dy[t] != t / 3 - 1 || p.tap_dx[t] != t % 3 - 1) return false;
+    if (!falnet_wgrad_canonical_taps9(p) || p.isy != 1 || p.isx != 1 || p.TH != p.IH || p.TW != p.IW) return false;
     if (p.gC % 32 || p.cin_total % 32 || p.nsrc < 1 || p.nsrc > 2) return false;
     int ctot = 0;
     for (int s = 0; s < p.nsrc; ++s) {
@@ -1659,7 +1656,7 @@ bool falnet_wgrad_rows_applicable(const falnet_wgrad_t& p) {
     return true;
 }
 
-int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, hipStream_t st) {
+int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, const WgradChoice& c, hipStream_t st) {
     const int w_rows = (p.gC + 31) / 32 * 32;
     const int ntci = (p.cin_total + 63) / 64, ntco = (w_rows + 63) / 64;
     const int ntiles = ntci * ntco;
@@ -1710,17 +1707,14 @@ int falnet_wgrad_rows_launch(const falnet_wgrad_t& p, hipStream_t st) {
     }
 #endif
     // the product kernel: v_mfma_f32_16x16x32 (round 5: -7 % on the launches alone, -0.9 % on the step: profiles/r05_ab_rows16.txt)
-    if (p.up2 == 2) {  // a `deconv` layer's weight gradient on the low-resolution grid, four parity classes per step: splits = pixel ranges
-        if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_up2q_kernel<f16_t, 2>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_up2q_kernel<bf16_t, 2>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
-        FALNET_RETURN_LAUNCH();
-    }
-    if (p.up2) {  // a `deconv` layer's weight gradient on the low-resolution grid: splits = (pixel range, parity class)
-        if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<f16_t, 4, 2, true>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<bf16_t, 4, 2, true>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
-        FALNET_RETURN_LAUNCH();
-    }
-    if (p.dtype == FALNET_F16) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<f16_t, 4, 2, false>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<bf16_t, 4, 2, false>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips);
+#define WR_UP2Q(TT) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_up2q_kernel<TT, 2>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips)
+#define WR_UP2(TT) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<TT, 4, 2, true>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips)
+#define WR_ROWS(TT) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_rows16_kernel<TT, 4, 2, false>), grid, dim3(WR8_THREADS), 0, st, p, w_rows, ntci, ntiles, nstrips)
+    if (c.up2 == 2) FALNET_DISPATCH_16(p.dtype, WR_UP2Q);  // a `deconv` layer's weight gradient on the low-resolution grid, four parity classes per step: splits = pixel ranges
+    else if (c.up2) FALNET_DISPATCH_16(p.dtype, WR_UP2);  // ... one class per split: splits = (pixel range, parity class)
+    else FALNET_DISPATCH_16(p.dtype, WR_ROWS);
+#undef WR_ROWS
+#undef WR_UP2
+#undef WR_UP2Q
     FALNET_RETURN_LAUNCH();
 }

@@ -33,6 +33,7 @@
 // (on the SOURCE address: the DMA destination is lane-linear), which makes the transposed reads of the two 4-pixel blocks a 32-lane half takes
 // (8 pixels apart) conflict-free for every column offset.
 #include "common.h"
+#include "wgrad_dispatch.h"
 
 typedef short wv_s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* wv_lptr_t;
@@ -584,7 +585,7 @@ bool falnet_wgrad_c3wave_applicable(const falnet_wgrad_t& p) {  // (the caller h
            (int64_t)p.B * ((p.TW + 31) / 32) * p.TH < (1ll << 30) && (int64_t)p.TW * p.gC * 2 < (1ll << 31);
 }
 
-int falnet_wgrad_c3wave_launch(const falnet_wgrad_t& p, hipStream_t st) {
+int falnet_wgrad_c3wave_launch(const falnet_wgrad_t& p, const WgradChoice&, hipStream_t st) {
     const int nstrips = (p.TW + 31) / 32;
 #define WC_L(T) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_c3wave_kernel<T>), dim3((unsigned)p.nsplit), dim3(WV_THREADS), 0, st, p, nstrips)
     FALNET_DISPATCH_16(p.dtype, WC_L);
@@ -596,11 +597,9 @@ int falnet_wgrad_c3wave_launch(const falnet_wgrad_t& p, hipStream_t st) {
 // stride 2 (TH = ceil(IH / 2), TW = ceil(IW / 2)): 64
 bool falnet_wgrad_wave_applicable(const falnet_wgrad_t& p) {
     if (p.dtype != FALNET_BF16 && p.dtype != FALNET_F16) return false;
-    if (p.ntaps != 9 || p.up2 || p.isy != p.isx || (p.isy != 1 && p.isy != 2)) return false;
+    if (!falnet_wgrad_canonical_taps9(p) || p.up2 || p.isy != p.isx || (p.isy != 1 && p.isy != 2)) return false;
     if (p.isy == 1 && (p.TH != p.IH || p.TW != p.IW)) return false;
     if (p.isy == 2 && (p.TH != (p.IH + 1) / 2 || p.TW != (p.IW + 1) / 2 || p.gC != 64)) return false;
-    for (int t = 0; t < 9; ++t)
-        if (p.tap_dy[t] != t / 3 - 1 || p.tap_dx[t] != t % 3 - 1) return false;
     if (p.nsrc != 1 || p.cin_total != 32 || p.src[0].C != 32 || p.src[0].H != p.IH || p.src[0].W != p.IW) return false;
     if (p.gC != 32 && p.gC != 64) return false;
     if (p.TW < 32 || p.nsplit < 1) return false;
@@ -609,14 +608,14 @@ bool falnet_wgrad_wave_applicable(const falnet_wgrad_t& p) {
     return true;
 }
 
-int falnet_wgrad_wave_launch(const falnet_wgrad_t& p, hipStream_t st) {
+int falnet_wgrad_wave_launch(const falnet_wgrad_t& p, const WgradChoice& c, hipStream_t st) {
     const int nstrips = (p.TW + 31) / 32;
     const dim3 grid((unsigned)p.nsplit);  // one slab per workgroup
 #define WV_K(T, NCO, S2) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad3x3_wave32_kernel<T, NCO, S2>), grid, dim3(WV_THREADS), 0, st, p, nstrips)
 #define WV_L(T)                                \
     do {                                       \
-        if (p.isy == 2) WV_K(T, 2, true);      \
-        else if (p.gC == 64) WV_K(T, 2, false); \
+        if (c.s2) WV_K(T, 2, true);            \
+        else if (c.nco == 2) WV_K(T, 2, false); \
         else WV_K(T, 1, false);                \
     } while (0)
     FALNET_DISPATCH_16(p.dtype, WV_L);

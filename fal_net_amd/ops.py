@@ -8,6 +8,7 @@ step is just that list replayed -- no per-step allocation, no Python tensor math
 import ctypes as C
 import os
 import sys
+import types
 
 import torch
 
@@ -646,49 +647,68 @@ def _autotune_conv(lib, d, ref, M, w_rows, Cout, reps=3):
     return best
 
 
-def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_pad, max_slabs, target_wgs=1536, up2=0):
-    """(variant, nsplit, kernel symbol) of one weight-gradient launch -- the host-side mirror of wgrad.hip's kernel choice
-    (falnet_wgrad re-checks the variant and fails loudly; whether the bias gradient is fused is ASKED from the library,
-    falnet_wgrad_fuses_bias, never re-derived here).  up2: falnet_wgrad_t::up2 (0, 1 = one parity class per split, 2 = all four per step)."""
+def _wgrad_plan_desc(d, max_slabs, target_wgs=1536, up2=0):
+    """(variant, nsplit, kernel symbol) of one weight-gradient launch, also left on the filled descriptor `d` (_fill_wgrad) with `up2`
+    (falnet_wgrad_t::up2: 0, 1 = one parity class per split, 2 = all four per step).  POLICY only: the order in which variants are tried, the A/B
+    switches, the conditions that are deliberately narrower than the library's, and the split count per kernel.  Whether a variant applies,
+    which kernel it then runs and that kernel's symbol are ASKED from the library (falnet_wgrad_kernel_name: the checks and the choice of
+    falnet_wgrad itself, so the split count is always the launched kernel's); the first candidate it accepts wins."""
+    lib = L.lib()
     up2 = int(up2)
-    M = B * TH * TW
-    h16 = dtype in (torch.bfloat16, torch.float16)
-    tn = TYPE_SYM[dtype]
-    dense = len(taps) == 9 and stride_in == 1 and TW >= 16  # halo-patch kernel (wgrad.hip: falnet_wgrad)
-    c3 = len(srcs) == 1 and srcs[0].C == 3  # planar f32 image source (ops.planar_src): first-layer kernel, variant 6
-    npatch = B * ((TH + 3) // 4) * ((TW + 31) // 32)
-    if c3:
-        assert h16 and dense and cout_pad == 32 and cin_pad == 32, "variant 6: 16-bit first layer, Cout 32"
-        variant, nsplit, sym = 6, max(1, min(_WGRAD_WGS, npatch)), f"_Z18wgrad3x3_c3_kernelI{tn}Ev14falnet_wgrad_tiiii"
-        if IW % 4 == 0 and TW >= 32 and not DETERMINISTIC:  # the wave-streaming form (csrc/wgrad_wave.hip: falnet_wgrad_c3wave_applicable)
-            nsplit = max(1, min(_WGRAD_WAVE_WGS, B * ((TW + 31) // 32) * TH // (8 * _WGRAD_WAVE_MIN_ROWS)))
-            sym = f"_Z22wgrad3x3_c3wave_kernelI{tn}Ev14falnet_wgrad_ti"
-    elif _wgrad_s2(dtype, taps, stride_in, TH, TW, IH, IW, srcs) and _wgrad_wave_s2(srcs, IH, IW, TW, cin_pad, cout_pad):
-        # wave-streaming kernel, stride-2 form (conv1's image source): a workgroup = ONE pixel range x 4 parity planes x 2 output-channel halves
-        units = B * ((TW + 31) // 32) * TH
-        nsplit = max(1, min(_WGRAD_WAVE_WGS, units // _WGRAD_WAVE_MIN_ROWS))
-        variant, sym = 9, f"_Z22wgrad3x3_wave32_kernelI{tn}Li2ELb1EEv14falnet_wgrad_ti"
-    elif _wgrad_s2(dtype, taps, stride_in, TH, TW, IH, IW, srcs) and _wgrad_rows_s2(srcs, IH, IW, TW, cin_pad, cout_pad):
+    B, TH, TW, cin_pad, cout_pad = d.B, d.TH, d.TW, d.cin_total, pad_c(d.gC)
+    on = lambda name: L.ab(name, "1") == "1"  # noqa: E731
+    strips = TW >= 32  # the streaming and stride-2 kernels work on 32-pixel strips: narrower maps stay on the halo-patch / per-tap kernels
+    cands = [6]  # the first layer's planar f32 image (ops.planar_src); refused for every other source
+    if d.isy == 2:
+        if strips and on("FALNET_WGRAD_S2"):
+            if on("FALNET_WGRAD_WAVE") and on("FALNET_WGRAD_WAVE_S2") and d.src[0].sx != 0:  # (a lone per-sample constant is no image to stream)
+                cands.append(9)  # wave-streaming kernel, stride-2 form (conv1's image source)
+            # row-streaming stride-2 kernel: 64 x 64 blocks per workgroup, a 32-channel side would idle half of its waves
+            if on("FALNET_WGRAD_ROWS_S2") and cin_pad >= int(L.ab("FALNET_WGRAD_ROWS_S2_MINCIN", "64")) and cout_pad >= 64:
+                cands.append(8)
+            cands.append(5)  # parity-plane halo kernel
+    elif strips:
+        if not up2 and on("FALNET_WGRAD_WAVE"):
+            cands.append(9)  # wave-streaming kernel: conv0_1's two convolutions, the skip group of the logits convolution
+        # row-streaming kernel: at least 64 channels on one side (a 64 x 64 block per workgroup; 32 -> 32 layers would leave three of its four
+        # waves idle); a 32-channel source under a 64 x 64 block idles half of the block's waves -> the 32 x 64 halo-patch kernel (variant 3)
+        if (on("FALNET_WGRAD_ROWS") and max(cin_pad, cout_pad) >= 64 and cin_pad != 32
+                and str(cin_pad) not in L.ab("FALNET_WGRAD_ROWS_SKIP_CIN", "").split(",")):  # A/B: leave layers of this input width on the patch kernel
+            cands.append(7)
+    if not up2:
+        # 32 (cin) x 64 (cout) channels per workgroup (variant 3): one gout fragment pair feeds twice the MFMAs (1.7 instead of 2.7 transposed LDS
+        # reads per MFMA).  In isolation -17 % on 64 -> 64 channel layers and -4 % on 128 -> 128; in the step (weight gradients are the longest
+        # chain of backward) +2.1 % pairs/s with the cut at 128 input channels, a little less with no cut (same-box A/B).
+        if on("FALNET_WGRAD_CO2") and cin_pad <= int(L.ab("FALNET_WGRAD_CO2_MAXCIN", "128")):
+            cands.append(3)
+        cands.append(0)
+    d.up2, d.nsplit = up2, 4  # (a count every kernel takes; the real one follows from the kernel the library names)
+    buf = C.create_string_buffer(160)
+    for variant in cands:
+        d.variant = variant
+        kid = lib.falnet_wgrad_kernel_name(C.byref(d), buf, 160)
+        if kid >= 0 and (kid != L.WGK_TAP or variant == 0):  # (the per-tap kernel is what variant 0 falls back to, no win for another variant)
+            break
+    else:
+        if up2:
+            raise ValueError("up2 weight gradient: the row-streaming kernel does not apply")
+        raise RuntimeError(f"weight gradient: no kernel takes this launch ({lib.falnet_last_error().decode(errors='replace')})")
+    sym = buf.value.decode()
+    units = B * ((TW + 31) // 32) * TH  # (sample, 32-pixel strip, row) units of the streaming kernels
+    npatch = B * ((TH + 3) // 4) * ((TW + 31) // 32)  # 4 x 32 patches of the halo kernels
+    if kid == L.WGK_C3:
+        nsplit = min(_WGRAD_WGS, npatch)
+    elif kid == L.WGK_C3WAVE:
+        nsplit = min(_WGRAD_WAVE_WGS, units // (8 * _WGRAD_WAVE_MIN_ROWS))
+    elif kid == L.WGK_WAVE:
+        # one workgroup = 8 waves, one slab.  Stride 1: 8 / (cout_pad / 32) pixel ranges per workgroup; stride 2: ONE pixel range x 4 parity planes x 2
+        # output-channel halves.  Every range gets at least _WGRAD_WAVE_MIN_ROWS strip rows (two of its steps are halo rows)
+        npw = 1 if d.isy == 2 else 8 // (cout_pad // 32)
+        nsplit = min(_WGRAD_WAVE_WGS, units // (npw * _WGRAD_WAVE_MIN_ROWS))
+    elif kid in (L.WGK_ROWS, L.WGK_ROWS_S2):
         tiles = ((cin_pad + 63) // 64) * ((cout_pad + 63) // 64)
-        units = B * ((TW + 31) // 32) * TH
-        nsplit = max(1, min(_WGRAD_ROWS_WGS // tiles, units // _WGRAD_ROWS_MIN_ROWS))
-        if nsplit >= 8:
-            nsplit -= nsplit % 8
-        variant, sym = 8, f"_Z23wgrad3x3_rows8s2_kernelI{tn}Li2EEv14falnet_wgrad_tiiii"
-    elif _wgrad_s2(dtype, taps, stride_in, TH, TW, IH, IW, srcs):
-        tiles = (cin_pad // 32) * (cout_pad // (64 if cout_pad % 64 == 0 else 32))
-        variant, nsplit = 5, max(1, min((_WGRAD_WGS + tiles - 1) // tiles, npatch))
-        sym = f"_Z18wgrad3x3_s2_kernelI{tn}Li{2 if cout_pad % 64 == 0 else 1}EEv14falnet_wgrad_tiiii"
-    elif _wgrad_wave(dtype, dense, srcs, IH, IW, TW, cin_pad, cout_pad) and not up2:
-        # wave-streaming kernel (32-channel input): one workgroup = 8 waves = 8 / (cout_pad / 32) pixel ranges, one slab per workgroup; every
-        # range gets at least _WGRAD_WAVE_MIN_ROWS strip rows (two of its steps are halo rows)
-        npw = 8 // (cout_pad // 32)
-        units = B * ((TW + 31) // 32) * TH
-        nsplit = max(1, min(_WGRAD_WAVE_WGS, units // (npw * _WGRAD_WAVE_MIN_ROWS)))
-        variant, sym = 9, f"_Z22wgrad3x3_wave32_kernelI{tn}Li{cout_pad // 32}ELb0EEv14falnet_wgrad_ti"
-    elif _wgrad_rows(dtype, dense, srcs, IH, IW, TW, cin_pad, cout_pad):
-        tiles = ((cin_pad + 63) // 64) * ((cout_pad + 63) // 64)
-        units = B * ((TW + 31) // 32) * TH * (4 if up2 == 1 else 1)  # up2 = 1: every parity class walks the whole low-resolution grid
+        if up2 == 1:
+            units *= 4  # every parity class walks the whole low-resolution grid
         nsplit = max(1, min(_WGRAD_ROWS_WGS // tiles, units // _WGRAD_ROWS_MIN_ROWS))
         if nsplit >= 8:
             nsplit -= nsplit % 8  # multiples of 8: the channel tiles of one pixel range then share an XCD
@@ -697,21 +717,29 @@ def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_p
             max_slabs -= max_slabs % 4
             if max_slabs < 4:
                 raise ValueError("up2 weight gradient: the slab budget holds fewer than four slabs")
-        variant, sym = 7, f"_Z22wgrad3x3_rows16_kernelI{tn}Li4ELi2ELb{int(up2 == 1)}EEv14falnet_wgrad_tiiii"
-        if up2 == 2:  # four parity classes per step (wgrad3x3_up2q_kernel): splits are plain ranges of low-resolution rows, any count
-            sym = f"_Z20wgrad3x3_up2q_kernelI{tn}Li2EEv14falnet_wgrad_tiiii"
-    elif up2:
-        raise ValueError("up2 weight gradient: the row-streaming kernel does not apply")
-    elif dense:
-        co2 = _wgrad_co2(dtype, dense, cin_pad, cout_pad)
-        tiles = (cin_pad // 32) * (cout_pad // 32) // (2 if co2 else 1)
-        nsplit = max(1, min((_WGRAD_WGS + tiles - 1) // tiles, npatch))
-        variant = 3 if co2 else 0
-        sym = f"_Z21wgrad3x3_patch_kernelI{tn}Li1ELi{2 if co2 else 1}EEv14falnet_wgrad_tiiii"
+    elif kid == L.WGK_S2:
+        tiles = (cin_pad // 32) * (cout_pad // (64 if cout_pad % 64 == 0 else 32))
+        nsplit = min((_WGRAD_WGS + tiles - 1) // tiles, npatch)
+    elif kid == L.WGK_PATCH:
+        tiles = (cin_pad // 32) * (cout_pad // 32) // (2 if variant == 3 else 1)
+        nsplit = min((_WGRAD_WGS + tiles - 1) // tiles, npatch)
     else:
-        tiles = ((cin_pad + 63) // 64) * ((cout_pad + 63) // 64) * len(taps)
-        variant, nsplit, sym = 0, max(1, min((target_wgs + tiles - 1) // tiles, (M + 255) // 256)), f"_Z12wgrad_kernelI{tn}Ev14falnet_wgrad_ti"
-    return variant, max(1, min(nsplit, max_slabs)), sym
+        tiles = ((cin_pad + 63) // 64) * ((cout_pad + 63) // 64) * d.ntaps
+        nsplit = min((target_wgs + tiles - 1) // tiles, (B * TH * TW + 255) // 256)
+    d.nsplit = max(1, min(nsplit, max_slabs))
+    assert lib.falnet_wgrad_kernel_name(C.byref(d), buf, 160) == kid and buf.value.decode() == sym, "the split count changed the library's kernel choice"
+    return variant, d.nsplit, sym
+
+
+def _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, cin_pad, cout_pad, max_slabs, target_wgs=1536, up2=0):
+    """_wgrad_plan_desc for a launch given by its geometry alone, before its operands exist: the plan of a scratch descriptor over `srcs` --
+    falnet_src_t (the library reads the image pointer's alignment), or any object with its C / H / W / sb / sy / sx, which gets an aligned
+    stand-in pointer -- and a stand-in gradient of `cout_pad` channels."""
+    d = L.Wgrad()
+    srcs = [s if isinstance(s, L.Src) else L.Src(1 << 20, s.C, s.H, s.W, s.sb, s.sy, s.sx) for s in srcs]
+    gout = types.SimpleNamespace(shape=(cout_pad,), data_ptr=lambda: 1 << 20)
+    _fill_wgrad(d, dtype, srcs, IH, IW, gout, [(t[0], t[1], 0) for t in taps], stride_in, B, TH, TW, types.SimpleNamespace(cout=cout_pad, cin_pad=cin_pad))
+    return _wgrad_plan_desc(d, max_slabs, target_wgs, up2)
 
 
 def _fill_wgrad(d, dtype, srcs, IH, IW, gout, taps, stride_in, B, TH, TW, pc):
@@ -749,10 +777,7 @@ def wgrad_calls(dtype, srcs, IH, IW, gout, taps, stride_in, B, TH, TW, pc, grad_
     gC = gout.shape[-1]
     M = B * TH * TW * (4 if up2 else 1)
     slab = len(taps) * pad_c(gC) * pc.cin_pad * 4
-    d.variant, nsplit, sym = _wgrad_plan(dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, pc.cin_pad, pad_c(gC), ws.numel() * 4 // slab,
-                                         target_wgs, up2=up2)
-    d.nsplit = nsplit
-    d.up2 = int(up2)
+    _, nsplit, sym = _wgrad_plan_desc(d, ws.numel() * 4 // slab, target_wgs, up2=up2)
     d.partial = ws.data_ptr()
     assert lib.falnet_wgrad_workspace_bytes(C.byref(d)) <= ws.numel() * 4, "wgrad workspace too small"
     ref = C.byref(d)
@@ -800,62 +825,6 @@ _WGRAD_WAVE_WGS = int(L.ab("FALNET_WGRAD_WAVE_WGS", "256"))  # workgroups of a w
 _WGRAD_WAVE_MIN_ROWS = int(L.ab("FALNET_WGRAD_WAVE_MIN_ROWS", "8"))
 
 
-def _wgrad_wave(dtype, dense, srcs, IH, IW, TW, cin_pad, cout_pad):
-    """Wave-streaming weight-gradient kernel (falnet_wgrad variant 9, csrc/wgrad_wave.hip): 16-bit dense 3x3 stride-1 layers over ONE
-    32-channel NHWC source at the launch size with 32 or 64 (padded) output channels -- conv0_1's two convolutions, the skip group of the
-    logits convolution."""
-    if not (dense and dtype in (torch.bfloat16, torch.float16) and TW >= 32 and cin_pad == 32 and cout_pad in (32, 64)):
-        return False
-    if len(srcs) != 1 or srcs[0].C != 32 or srcs[0].H != IH or srcs[0].W != IW:
-        return False
-    return L.ab("FALNET_WGRAD_WAVE", "1") == "1"
-
-
-def _wgrad_wave_s2(srcs, IH, IW, TW, cin_pad, cout_pad):
-    """The stride-2 form of the wave-streaming kernel (falnet_wgrad variant 9 with isy = 2): ONE 32-channel NHWC source at the input size, 64 output
-    channels -- conv1's image source (its constant `flow` channel goes through falnet_wgrad_const_plane)."""
-    return (len(srcs) == 1 and srcs[0].C == 32 and srcs[0].H == IH and srcs[0].W == IW and srcs[0].sx != 0 and cin_pad == 32 and cout_pad == 64
-            and TW >= 32 and L.ab("FALNET_WGRAD_WAVE", "1") == "1" and L.ab("FALNET_WGRAD_WAVE_S2", "1") == "1")
-
-
-def _wgrad_rows(dtype, dense, srcs, IH, IW, TW, cin_pad, cout_pad):
-    """Row-streaming weight-gradient kernel (falnet_wgrad variant 7, csrc/wgrad_rows.hip): 16-bit dense 3x3 stride-1 layers with
-    at least 64 channels on one side (a 64 x 64 block per workgroup; 32 -> 32 layers would leave three of its four waves idle),
-    32-pixel strips, sources at the launch size or exactly half of it."""
-    if not (dense and dtype in (torch.bfloat16, torch.float16) and TW >= 32 and max(cin_pad, cout_pad) >= 64):
-        return False
-    if cin_pad == 32:  # a 32-channel source under a 64 x 64 block: half of the block's waves idle -> the 32 x 64 halo-patch kernel (variant 3)
-        return False
-    if any(not ((s.H == IH or 2 * s.H == IH) and (s.W == IW or 2 * s.W == IW)) or s.C % 32 for s in srcs):
-        return False
-    if str(cin_pad) in L.ab("FALNET_WGRAD_ROWS_SKIP_CIN", "").split(","):  # A/B: leave layers of this input width on the patch kernel
-        return False
-    return L.ab("FALNET_WGRAD_ROWS", "1") == "1"
-
-
-def _wgrad_rows_s2(srcs, IH, IW, TW, cin_pad, cout_pad):
-    """Row-streaming stride-2 weight gradient (falnet_wgrad variant 8, csrc/wgrad_rows.hip): one NHWC source at the input size with at
-    least 64 input channels (64 x 64 blocks per workgroup: a 32-channel source would idle half of its waves), 32-pixel strips."""
-    return (len(srcs) == 1 and srcs[0].H == IH and srcs[0].W == IW and srcs[0].sx != 0 and cin_pad >= int(L.ab("FALNET_WGRAD_ROWS_S2_MINCIN", "64")) and cout_pad >= 64 and TW >= 32
-            and L.ab("FALNET_WGRAD_ROWS_S2", "1") == "1")
-
-
-def _wgrad_s2(dtype, taps, stride_in, TH, TW, IH, IW, srcs):
-    """Parity-plane halo kernel for 3x3 stride-2 weight gradients (falnet_wgrad variant 5): bf16, canonical taps, sources at
-    the input size (or per-sample constants)."""
-    return (dtype in H16 and len(taps) == 9 and stride_in == 2 and TW >= 32 and TH == (IH + 1) // 2 and TW == (IW + 1) // 2
-            and all((s.H == IH and s.W == IW) or (s.sy == 0 and s.sx == 0) for s in srcs)
-            and L.ab("FALNET_WGRAD_S2", "1") == "1")
-
-
-def _wgrad_co2(dtype, dense, cin_pad, cout_pad):
-    """32 (cin) x 64 (cout) channels per workgroup (falnet_wgrad variant 3): one gout fragment pair feeds twice the MFMAs
-    (1.7 instead of 2.7 transposed LDS reads per MFMA).  In isolation -17 % on 64 -> 64 channel layers and -4 % on 128 -> 128;
-    in the step (weight gradients are the longest chain of backward) +2.1 % pairs/s with the cut at 128 input channels, a little
-    less with no cut (same-box A/B)."""
-    return dense and dtype in H16 and cin_pad <= int(L.ab("FALNET_WGRAD_CO2_MAXCIN", "128")) and cout_pad % 64 == 0 and L.ab("FALNET_WGRAD_CO2", "1") == "1"
-
-
 class WgradBatch:
     """All weight / bias gradients of one backward pass: per-layer split-K wgrad launches (each with its OWN slab
     region, so they can run back to back) followed by ONE batched slab reduce and ONE batched bias-gradient launch
@@ -879,10 +848,7 @@ class WgradBatch:
         gC = gout.shape[-1]
         M = B * TH * TW * (4 if up2 else 1)
         slab = len(taps) * pad_c(gC) * pc.cin_pad * 4
-        d.variant, nsplit, sym = _wgrad_plan(self.dtype, srcs, taps, stride_in, B, TH, TW, IH, IW, pc.cin_pad, pad_c(gC), max(1, self.SLAB_CAP // slab),
-                                             up2=up2)
-        d.nsplit = nsplit
-        d.up2 = int(up2)
+        _, nsplit, sym = _wgrad_plan_desc(d, max(1, self.SLAB_CAP // slab), up2=up2)
         ref = C.byref(d)
         keep = (d, srcs, gout, grad_w, grad_b)
 

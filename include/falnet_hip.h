@@ -232,7 +232,7 @@ typedef struct {
                                   9 wave-streaming kernel (csrc/wgrad_wave.hip; bf16 / f16, dense 3x3, ONE 32-channel NHWC source at the input size):
                                   stride 1 with gC 32 or 64, or stride 2 (TH = ceil(IH / 2), TW = ceil(IW / 2)) with gC 64; nsplit = workgroups =
                                   slabs, every wave streams its own (sample, strip, row) range (stride 2: its own parity plane of one range).
-                                  Variant 6 takes the same wave-streaming form when IW % 4 == 0 (not in deterministic mode) */
+                                  Variant 6 takes the same wave-streaming form when IW % 4 == 0 (not in deterministic mode): FALNET_WGK_C3WAVE */
     float* bias_grad;          /* optional, halo kernels (dense 3x3 stride 1, variant 5): db[co] += sum over positions of gout[.,co]
                                   (f32 atomics, [gC]) from the gout tiles the kernel stages anyway -- replaces a falnet_bias_grad
                                   pass over the same tensor.  Only the kernels falnet_wgrad_fuses_bias() reports fuse it;
@@ -253,6 +253,23 @@ typedef struct {
 int falnet_wgrad_fuses_bias(const falnet_wgrad_t* p);
 int64_t falnet_wgrad_workspace_bytes(const falnet_wgrad_t* p);
 int falnet_wgrad(const falnet_wgrad_t* p, void* stream);
+/* The kernels behind falnet_wgrad.  Which one a descriptor gets is decided in ONE place in the library; a host that sizes `nsplit` per kernel
+ * asks falnet_wgrad_kernel_name and restates none of the applicability rules. */
+enum {
+    FALNET_WGK_TAP = 0,     /* per-tap kernel: any taps, stride and dtype (variants 0 / 1 / 3 / 4 where the launch is not dense 3x3 stride 1, TW >= 16) */
+    FALNET_WGK_PATCH = 1,   /* halo-patch kernel, 32x32 (variant 0), 32x64 (3) or 64x32 (4) channels per workgroup */
+    FALNET_WGK_S2 = 2,      /* parity-plane halo kernel (variant 5) */
+    FALNET_WGK_C3 = 3,      /* first layer, halo-patch form (variant 6) */
+    FALNET_WGK_C3WAVE = 4,  /* first layer, wave-streaming form (variant 6: IW % 4 == 0, TW >= 32, a 16-byte aligned image, not in deterministic mode) */
+    FALNET_WGK_ROWS = 5,    /* row-streaming kernel and its two up2 forms (variant 7) */
+    FALNET_WGK_ROWS_S2 = 6, /* row-streaming kernel, stride 2 (variant 8) */
+    FALNET_WGK_WAVE = 7     /* wave-streaming kernel, stride 1 and stride 2 (variant 9) */
+};
+/* The kernel falnet_wgrad would launch for this descriptor: the same checks and the same choice, nothing issued, no pointer dereferenced (the
+ * image pointer's alignment is read), `partial` and `bias_grad` not needed.  Returns the FALNET_WGK_* id (>= 0) and writes the mangled symbol
+ * of the instantiation -- the name rocprofv3 reports -- into buf; a descriptor falnet_wgrad refuses gives a negative value and the same
+ * falnet_last_error text. */
+int falnet_wgrad_kernel_name(const falnet_wgrad_t* p, char* buf, int len);
 /* partial [nsplit][ntaps][CoutPad][CinTot] -> grad OIHW f32 [Cout][Cin][kh][kw] (taps in kh*kw+kw order) */
 /* channel groups as in falnet_pack_weights: packed column cp holds real channel cp (cp < c0_real) or
  * c0_real + (cp - c0_pad) */

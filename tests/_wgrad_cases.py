@@ -2,7 +2,7 @@
 through the C ABI (fal_net_amd._lib.Wgrad filled by fal_net_amd.ops._fill_wgrad, the variant forced on the descriptor) and holds it to
 tests/_wgrad_ref.py with torch.equal: operands are small integers, so every f32 sum is exact (see _wgrad_ref.py).
 
-A case is a dict (see _c): the kernel instantiation it is meant to reach (`kernel`, named in the test ids), the variant forced, the
+A case is a dict (see _c): the kernel instantiation it reaches (`kernel`, named in the test ids; KERNEL_TABLE), the variant forced, the
 shape, the source forms and the split counts.  The module imports without a GPU; the CPU tests check the exactness condition of every
 case and that every kernel has a case whose largest |dW| is at least 4096 (a 16-bit intermediate could not pass).
 
@@ -79,7 +79,7 @@ CASES = [
     _c("c3_wave_5x32", "wgrad3x3_c3wave_kernel<T>", 6, 1, [3], 32, 5, 32, (1, 3, PLAN), forms=["planar"], c3form="wave"),
     _c("c3_patch_37x70", "wgrad3x3_c3_kernel<T>", 6, 1, [3], 32, 37, 70, (1, 3, PLAN), forms=["planar"], c3form="patch"),
     _c("c3_patch_75x250", "wgrad3x3_c3_kernel<T>", 6, 1, [3], 32, 75, 250, (1, 3, PLAN), forms=["planar"], c3form="patch"),
-    _c("c3_misaligned_16x64", "wgrad3x3_c3_kernel<T>", 6, 2, [3], 32, 16, 64, (1, 3, 20), forms=["planar"], c3form="patch", misalign=True,
+    _c("c3_misaligned_16x64", "wgrad3x3_c3_kernel<T>", 6, 2, [3], 32, 16, 64, (1, 3, 20, PLAN), forms=["planar"], c3form="patch", misalign=True,
        same_operands_as="c3_wave_16x64"),
     _c("c3_wave_odd_grid_5x32", "wgrad3x3_c3wave_kernel<T>", 6, 2, [3], 32, 5, 32, (1, 3), forms=["planar"], c3form="wave", image="odd_grid"),
     _c("c3_patch_odd_grid_6x35", "wgrad3x3_c3_kernel<T>", 6, 1, [3], 32, 6, 35, (1, 3), forms=["planar"], c3form="patch", image="odd_grid"),
@@ -120,6 +120,24 @@ CASES = [
 BY_NAME = {c["name"]: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 KERNELS = sorted({c["kernel"] for c in CASES})
+# `kernel` field -> (id falnet_wgrad_kernel_name returns: fal_net_amd._lib.WGK_*, the symbol with {T} = the mangled operand type, whether
+# the kernel sums the bias gradient): what a case must reach, spelled out (tests/test_wgrad_plan_host.py)
+KERNEL_TABLE = {
+    "wgrad_kernel": (0, "_Z12wgrad_kernelI{T}Ev14falnet_wgrad_ti", False),
+    "wgrad3x3_patch_kernel<T,1,1>": (1, "_Z21wgrad3x3_patch_kernelI{T}Li1ELi1EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_patch_kernel<T,1,2>": (1, "_Z21wgrad3x3_patch_kernelI{T}Li1ELi2EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_patch_kernel<T,2,1>": (1, "_Z21wgrad3x3_patch_kernelI{T}Li2ELi1EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_s2_kernel<T,1>": (2, "_Z18wgrad3x3_s2_kernelI{T}Li1EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_s2_kernel<T,2>": (2, "_Z18wgrad3x3_s2_kernelI{T}Li2EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_c3_kernel<T>": (3, "_Z18wgrad3x3_c3_kernelI{T}Ev14falnet_wgrad_tiiii", True),
+    "wgrad3x3_c3wave_kernel<T>": (4, "_Z22wgrad3x3_c3wave_kernelI{T}Ev14falnet_wgrad_ti", True),
+    "wgrad3x3_rows16_kernel<T,4,2,false>": (5, "_Z22wgrad3x3_rows16_kernelI{T}Li4ELi2ELb0EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_rows16_kernel<T,4,2,true>": (5, "_Z22wgrad3x3_rows16_kernelI{T}Li4ELi2ELb1EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_rows8s2_kernel<T,2>": (6, "_Z23wgrad3x3_rows8s2_kernelI{T}Li2EEv14falnet_wgrad_tiiii", True),
+    "wgrad3x3_wave32_kernel<T,1,false>": (7, "_Z22wgrad3x3_wave32_kernelI{T}Li1ELb0EEv14falnet_wgrad_ti", True),
+    "wgrad3x3_wave32_kernel<T,2,false>": (7, "_Z22wgrad3x3_wave32_kernelI{T}Li2ELb0EEv14falnet_wgrad_ti", True),
+    "wgrad3x3_wave32_kernel<T,2,true>": (7, "_Z22wgrad3x3_wave32_kernelI{T}Li2ELb1EEv14falnet_wgrad_ti", True),
+}
 # one case per kernel for the deterministic-mode child (tests/_wgrad_det.py) and the mutation tests
 DET_CASES = ["tap_two_sources_8x16", "patch11_12x40_c49", "patch12_9x33", "patch21_37x64", "s2_24x71_two_sources", "s2_9x66_c96",
              "c3_wave_16x64", "c3_patch_37x70", "rows_straddle_12x40_c49", "rows_up2_9x33", "rows_s2_9x66_c96", "wave_12x40_c49", "wave_9x33",
@@ -360,9 +378,25 @@ def range_start_pixel(case, nranges, k=1):
 
 def c3_form(case, out, nsplit):
     """Which form of variant 6 ran, from the slabs: the patch form gives split s the patches [s pps, (s + 1) pps), so with more splits
-    than patches the slabs from npatch on are exact zeros; the wave form cuts (sample, strip, row) units and fills them."""
+    than patches the slabs from npatch on are exact zeros; the wave form cuts (sample, strip, row) units and fills them.  With at most
+    as many splits as patches (the patch form's planned count) the centre tap tells: in the patch form, and only there, every slab holds
+    the products of exactly its patches' pixels (4 x 32 patches numbered sample, patch row, patch column; needs two slabs at least)."""
     g = geom(case)
-    assert nsplit > g["npatch"], "tell the forms apart with more splits than patches"
     n = 9 * 32 * 32
-    tail = out["ws"][g["npatch"] * n:nsplit * n].view(-1, 9, 32, 32)[..., :3]
-    return "patch" if bool((tail == 0).all()) else "wave"
+    if nsplit > g["npatch"]:
+        tail = out["ws"][g["npatch"] * n:nsplit * n].view(-1, 9, 32, 32)[..., :3]
+        return "patch" if bool((tail == 0).all()) else "wave"
+    assert nsplit >= 2 and case.get("image") != "odd_grid", "one slab holds the same sums in both forms"
+    desc = g["desc"]
+    B, TH, TW = desc["B"], desc["TH"], desc["TW"]
+    (img,), gout = host_operands(case)
+    ty, tx = (TH + 3) // 4, (TW + 31) // 32
+    pps = (g["npatch"] + nsplit - 1) // nsplit
+    owner = torch.arange(B).view(B, 1, 1) * ty * tx + (torch.arange(TH) // 4).view(1, TH, 1) * tx + (torch.arange(TW) // 32).view(1, 1, TW)
+    centre = out["ws"][:nsplit * n].view(nsplit, 9, 32, 32)[:, 4, :, :3].to(torch.float64).cpu()
+    for s in range(nsplit):
+        mine = ((owner // pps) == s).to(torch.float64)
+        want = torch.einsum("byxo,bcyx->oc", gout[..., :32].to(torch.float64) * mine.unsqueeze(-1), img.to(torch.float64))
+        if not torch.equal(centre[s], want):
+            return "wave"
+    return "patch"

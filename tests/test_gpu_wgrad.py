@@ -43,7 +43,8 @@ def test_wgrad_exact(case, dtype):
     """Every split count of the case; PLAN = the (variant, nsplit) fal_net_amd.ops._wgrad_plan returns, whose variant must be the case's."""
     K.exactness(case)
     for nsplit in K.split_counts(case):
-        if nsplit == K.PLAN:
+        planned = nsplit == K.PLAN
+        if planned:
             variant, nsplit = K.planned(case, dtype, DEV)
             assert variant == case["variant"], (case["name"], variant)
         out = K.run_case(case, dtype, nsplit, DEV)
@@ -53,6 +54,8 @@ def test_wgrad_exact(case, dtype):
             assert out["fuses_bias"] == 0, out["what"]
         if case["forms"] == ["planar"] and nsplit > K.geom(case)["npatch"]:
             assert K.c3_form(case, out, nsplit) == case["c3form"], out["what"]
+        if planned and case.get("misalign"):  # the plan asked the library: the patch form's split count, and the patch form in the slabs
+            assert nsplit == min(256, K.geom(case)["npatch"]) >= 2 and K.c3_form(case, out, nsplit) == "patch", out["what"]
 
 
 def test_first_layer_forms():
