@@ -22,6 +22,8 @@ their hole-filled versions, fal_net_amd/inpaint.py;
 fal_net_amd/sparsification.py;
 `--pseudo-lidar [--pl-beams N ...]` adds each frame's depth as a Velodyne-format scan Pseudo_lidar/<frame>.bin, fal_net_amd/pseudo_lidar.py;
 `--mesh [--mesh-max-jump T ...]` adds each frame's depth as a triangle mesh Mesh/<frame>.ply, cut where depth jumps, fal_net_amd/mesh.py;
+`--min-component K [--component-jump T]` drops from the mesh and the scan the pixels in connected pieces of the disparity map smaller than K pixels,
+fal_net_amd/components.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -278,6 +280,31 @@ parser.add_argument('--mesh-normals', action='store_true', help='--mesh: per-ver
 MESH_ARGS = ('mesh', 'mesh_max_jump', 'mesh_max_depth', 'mesh_min_conf', 'mesh_normals')
 
 
+def _min_component(v):
+    from fal_net_amd.components import check_min_component
+    try:
+        return check_min_component(int(v), '--min-component')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _component_jump(v):
+    x = float(v)
+    if not x >= 0.0:
+        raise argparse.ArgumentTypeError('--component-jump needs a number >= 0 (inf: all valid neighbours joined), got {}'.format(v))
+    return x
+
+
+parser.add_argument('--min-component', type=_min_component, default=None, metavar='K',
+                    help='--mesh / --pseudo-lidar: a speckle filter -- keep only the pixels whose connected component of the disparity map (4-neighbours '
+                         'joined where the disparities differ by at most the factor 1 + --component-jump; fal_net_amd/components.py, labelled on the device) '
+                         'holds at least K pixels, and one JSON line with the component counts')
+parser.add_argument('--component-jump', type=_component_jump, default=None, metavar='T',
+                    help='--min-component: two neighbours belong together when their disparities differ by at most the factor 1 + T (default: '
+                         '--mesh-max-jump for the mesh, 0.05 for the scan)')
+COMPONENT_ARGS = ('min_component', 'component_jump')
+
+
 SPARSIFICATION_SCORES = ('std', 'entropy', 'conf', 'relstd')  # fal_net_amd/sparsification.py: SCORES
 
 parser.add_argument('--sparsification', type=_comma_list(SPARSIFICATION_SCORES, '--sparsification takes a comma-separated subset of {choices} (each once), got {v!r}',
@@ -311,10 +338,28 @@ def hidden_settings(a):
     return tuple(n for _, names, on, _ in FAMILIES if not on(a) for n in names)
 
 
+# Families added after hidden_settings() was pinned to the table above: the same four-tuples, walked after FAMILIES by check_family_args and by the
+# settings.txt filter (settings_hidden)
+LATER_FAMILIES = (
+    ('--min-component', COMPONENT_ARGS, lambda a: a.min_component is not None, True),
+)
+
+
+def settings_hidden(a):
+    """What settings.txt leaves out: hidden_settings, then the names of every later family that is off."""
+    return hidden_settings(a) + tuple(n for _, names, on, _ in LATER_FAMILIES if not on(a) for n in names)
+
+
+def check_component_args(a):
+    """--min-component filters the products that have pixels to drop; SystemExit names them when neither is on."""
+    if a.min_component is not None and not (a.mesh or a.pseudo_lidar):
+        raise SystemExit('--min-component filters the products of --mesh and --pseudo-lidar: add --mesh or --pseudo-lidar')
+
+
 def check_family_args(a):
     """A family's parameters change nothing without its switch: SystemExit names the ones that were given (the families whose parameters are
     refused; --sweep-range and the --freeview path parameters are accepted in silence)."""
-    for switch, names, on, strict in FAMILIES:
+    for switch, names, on, strict in FAMILIES + LATER_FAMILIES:
         given = [] if on(a) or not strict else [n for n in names[1:] if getattr(a, n) != parser.get_default(n)]
         if given:
             raise SystemExit('{} {} a parameter of {}: add {}'.format(', '.join('--' + n.replace('_', '-') for n in given),
@@ -416,7 +461,7 @@ def refuse_out_of_scope(a):
                          'run without them to evaluate'.format(', '.join('-' + n for n in on)))
 
 
-LINE_ORDER = ('view', 'sparsification', 'pseudo_lidar', 'mesh', 'sweep', 'freeview', 'stats')  # of the products' JSON lines, as they were added
+LINE_ORDER = ('view', 'sparsification', 'pseudo_lidar', 'mesh', 'sweep', 'freeview', 'stats', 'components')  # of the products' JSON lines, as they were added
 
 
 def extra_lines(products):
@@ -447,6 +492,7 @@ def main():
     check_freeview_fill_args(args)
     check_confidence_args(args)
     check_family_args(args)
+    check_component_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     check_sparsification_args(args, dataset_mode)
     model_dir = checkpoint_path(args)  # :119-120
@@ -507,10 +553,19 @@ def main():
                 print('=> pseudo-LiDAR: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
                       'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
             products.append(pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
-                                                           max_height=args.pl_max_height, min_conf=args.pl_min_conf, extra={'calibration': source}))
+                                                           max_height=args.pl_max_height, min_conf=args.pl_min_conf, extra={'calibration': source},
+                                                           **({} if args.min_component is None else
+                                                              {'min_component': args.min_component,
+                                                               'component_jump': 0.05 if args.component_jump is None else args.component_jump})))
         if args.mesh:
             products.append(mesh.MeshWriter(save_path, max_jump=args.mesh_max_jump, max_depth=args.mesh_max_depth, min_conf=args.mesh_min_conf,
-                                            normals=args.mesh_normals, ply_format=args.ply_format))
+                                            normals=args.mesh_normals, ply_format=args.ply_format,
+                                            **({} if args.min_component is None else
+                                               {'min_component': args.min_component, 'component_jump': args.component_jump})))
+        if args.min_component is not None:
+            from fal_net_amd import components
+            jump = args.component_jump if args.component_jump is not None else (args.mesh_max_jump if args.mesh else 0.05)
+            products.append(components.ComponentsSummary(args.min_component, jump))
         return products
 
     if dataset_mode:
@@ -529,7 +584,7 @@ def main():
         loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            hidden = hidden_settings(args)
+            hidden = settings_hidden(args)
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         products = make_products(triples)

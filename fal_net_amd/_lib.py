@@ -220,6 +220,8 @@ SIGNATURES = {
     "falnet_velo_unproject": [_P, _D, _P, _F, _P, _F, _P, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P],
     "falnet_mesh_workspace_bytes": [_I, _I],
     "falnet_mesh_build": [_P, _F, _F, _F, _F, _P, _D, _D, _P, _F, _F, _F, _D, _I, _I, _I, _P, _P, _P, _P, _P],
+    "falnet_components_workspace_bytes": [_I, _I, _I],
+    "falnet_components": [_P, _P, _F, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P],
     "falnet_sort_u32_workspace_bytes": [_L, _I],
     "falnet_sort_u32": [_P, _L, _I, _P, _P, _P],
     "falnet_sparsify_workspace_bytes": [_I, _I, _I],
@@ -229,7 +231,8 @@ _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
              "falnet_lidar_workspace_bytes": C.c_int64, "falnet_sort_u32_workspace_bytes": C.c_int64,
              "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64,
-             "falnet_inpaint_workspace_bytes": C.c_int64, "falnet_mesh_workspace_bytes": C.c_int64}
+             "falnet_inpaint_workspace_bytes": C.c_int64, "falnet_mesh_workspace_bytes": C.c_int64,
+             "falnet_components_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

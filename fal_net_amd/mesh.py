@@ -124,13 +124,23 @@ def save_ply(file_name, vertices, faces, normals=False, ply_format="binary"):
 class MeshWriter:
     """Test_KITTI.py --mesh: writes Mesh/{frame:010d}.ply under `save_path`, the frame's depth mesh with the camera of dumps.camera_for_width.  Its
     folder is its own, as dumps.SweepWriter's: FrameWriter and DUMP_KINDS do not know about it.  min_conf: with it, write() needs the frame's
-    confidence map and only vertices of conf >= min_conf are valid."""
+    confidence map and only vertices of conf >= min_conf are valid.
+    min_component = K: a speckle filter.  The frame's component sizes (components.size_score of the disparity, joined at component_jump -- default:
+    max_jump --, the depth bounds as disparity bounds lo = fb / max_depth and hi = fb / min_depth or infinity, and with min_conf the confidence map as
+    the components' score, so that a low-confidence pixel has size 0) become build's score with threshold K: only the vertices in components of at
+    least K pixels are valid, and build sees only the size map.  An approximation at the bounds: the components judge the bound on the disparity, build
+    on its own f32 chain z = fb / (d + 1e-4f), so a pixel within rounding of a bound can count towards a size and still be dropped by build, or the
+    reverse."""
     key = "mesh"
 
-    def __init__(self, save_path, max_jump=0.05, max_depth=80.0, min_depth=0.0, min_conf=None, normals=False, ply_format="binary"):
+    def __init__(self, save_path, max_jump=0.05, max_depth=80.0, min_depth=0.0, min_conf=None, normals=False, ply_format="binary", min_component=None,
+                 component_jump=None):
+        from .components import check_jump, check_min_component
         check_depths(float(min_depth), float(max_depth), float(max_jump))
         check_min_conf(min_conf)
         check_ply_format(ply_format)
+        self.min_component = check_min_component(min_component)
+        self.component_jump = check_jump(max_jump if component_jump is None else component_jump, "component_jump")
         self.save_path, self.min_conf, self.normals, self.ply_format = save_path, min_conf, bool(normals), ply_format
         self.kw = dict(max_jump=float(max_jump), max_depth=float(max_depth), min_depth=float(min_depth))
         self.folder = os.path.join(save_path, "Mesh")
@@ -152,8 +162,14 @@ class MeshWriter:
             raise ValueError("MeshWriter: min_conf = {} needs the frame's confidence map".format(self.min_conf))
         use = self.min_conf is not None
         focal, baseline = dumps.camera_for_width(disp.shape[-1])
-        meshes, counts = build(left, disp, focal, baseline, score=conf if use else None, threshold=self.min_conf if use else None, normals=self.normals,
-                               **self.kw)
+        score, threshold = (conf, self.min_conf) if use else (None, None)
+        if self.min_component is not None:
+            from . import components
+            fb, lo_z = focal * baseline, self.kw["min_depth"]
+            score = components.size_score(disp, self.component_jump, lo=fb / self.kw["max_depth"], hi=fb / lo_z if lo_z > 0.0 else float("inf"),
+                                          score=score, threshold=threshold).view(disp.shape)
+            threshold = float(self.min_component)
+        meshes, counts = build(left, disp, focal, baseline, score=score, threshold=threshold, normals=self.normals, **self.kw)
         save_ply(self.file(i), meshes[0][0], meshes[0][1], normals=self.normals, ply_format=self.ply_format)
         self.frames += 1
         self.vertices += counts[0][0]
@@ -170,4 +186,6 @@ class MeshWriter:
                "normals": self.normals}
         if self.min_conf is not None:
             out["min_conf"] = self.min_conf
+        if self.min_component is not None:
+            out["min_component"] = self.min_component
         return out

@@ -117,14 +117,22 @@ class PseudoLidarWriter:
     """Test_KITTI.py --pseudo-lidar: writes Pseudo_lidar/{frame:010d}.bin under `save_path`, the frame's disparity back-projected with the
     parameters given here.  calibration: a callable (frame index, H, W) -> (P, fb) -- frame() asks it per frame -- or None when
     write() is always given both.  min_conf: with it, write() needs the frame's confidence map and keeps only the pixels of conf >= min_conf.
-    extra: what summary() says besides the counts."""
+    extra: what summary() says besides the counts.
+    min_component = K: a speckle filter.  The frame's component sizes (components.size_score of the disparity, joined at component_jump, the depth
+    bounds as disparity bounds lo = fb / max_depth and hi = fb / min_depth or infinity, and with min_conf the confidence map as the components' score,
+    so that a low-confidence pixel has size 0) become unproject's score with threshold K: only the pixels in components of at least K pixels are kept,
+    and unproject sees only the size map.  An approximation: the components judge the bound on the disparity, unproject on its own f64 depth
+    fb / disparity, so a pixel within rounding of a bound can count towards a size and still be dropped by unproject, or the reverse; and the scan's
+    x > 0 and max_height tests do not enter the graph -- a component is counted with the pixels those tests drop afterwards."""
     key = "pseudo_lidar"
 
     def __init__(self, save_path, calibration=None, beams=0, az_bins=1024, max_depth=80.0, max_height=1.0, min_conf=None, min_depth=0.0,
-                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0), extra=None):
+                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0), extra=None, min_component=None, component_jump=0.05):
+        from .components import check_jump, check_min_component
         if beams != 0:
             edge_tables(beams, az_bins, elevation, azimuth)  # the range checks, before the first frame
         check_min_conf(min_conf)
+        self.min_component, self.component_jump = check_min_component(min_component), check_jump(component_jump, "component_jump")
         if not np.isfinite(max_depth) or not max_depth > min_depth:
             raise ValueError("max_depth must be finite and above min_depth, got {}".format(max_depth))
         self.save_path, self.calibration, self.min_conf, self.extra = save_path, calibration, min_conf, dict(extra or {})
@@ -149,7 +157,16 @@ class PseudoLidarWriter:
         if self.min_conf is not None and conf is None:
             raise ValueError("PseudoLidarWriter: min_conf = {} needs the frame's confidence map".format(self.min_conf))
         use = self.min_conf is not None
-        pts = unproject(disp, P, fb=fb, score=conf if use else None, threshold=self.min_conf if use else None, **self.kw)
+        score, threshold = (conf, self.min_conf) if use else (None, None)
+        if self.min_component is not None:
+            from . import components
+            lo_z, hi_z = self.kw["min_depth"], self.kw["max_depth"]
+            # a disparity's bounds are the depth bounds through fb; a depth map (fb None) takes them as they are
+            lo, hi = (lo_z, hi_z) if fb is None else (fb / hi_z, fb / lo_z if lo_z > 0.0 else float("inf"))
+            if score is not None:
+                score = score.reshape(disp.shape)
+            score, threshold = components.size_score(disp, self.component_jump, lo=lo, hi=hi, score=score, threshold=threshold), float(self.min_component)
+        pts = unproject(disp, P, fb=fb, score=score, threshold=threshold, **self.kw)
         n = write_bin(self.file(i), pts)
         self.frames += 1
         self.points += n
@@ -164,4 +181,6 @@ class PseudoLidarWriter:
             out["az_bins"] = self.kw["az_bins"]
         if self.min_conf is not None:
             out["min_conf"] = self.min_conf
+        if self.min_component is not None:
+            out["min_component"] = self.min_component
         return dict(out, **self.extra)

@@ -876,6 +876,32 @@ int falnet_mesh_build(const float* img, float mean_r, float mean_g, float mean_b
                       const float* score, float threshold, float min_depth, float max_depth, double max_jump, int H, int W, int with_normals,
                       void* vertices_out, void* faces_out, int64_t* counts_dev, void* workspace, void* stream);
 
+/* ---- Connected components of a depth or disparity map (csrc/components.hip; fal_net_amd/components.py) ------------------------------------------------
+ * map: B maps of H x W f32, one after the other; pixel g = i W + j of a map has the value v_g.  The map is taken as given, depth or disparity: the
+ * edge test is a ratio and means the same on either (the numpy restatement is tests/_components_ref.py).
+ *   valid pixel   lo < v_g && v_g <= hi, and with score (B x H x W f32, may be NULL) also score_g >= threshold; every comparison with a NaN is false.
+ *                 0 <= lo < hi; hi may be +infinity; a NaN bound is refused.
+ *   edge          two 4-neighbours p, q (right, down) are joined iff both are valid and max(v_p, v_q) <= min(v_p, v_q) * ratio: one correctly rounded
+ *                 f32 multiply, the keep rule of falnet_mesh_build, whose ratio = (float)(1.0 + max_jump) the caller forms in double and rounds once.
+ *                 ratio >= 1; +infinity joins all valid neighbours; a NaN is refused.  A tie joins.
+ *   component     a connected set of that graph.
+ *   label         (int32, B x H x W, may be NULL: not wanted) label_g = the smallest pixel index of g's component, -1 for an invalid pixel.  Indices
+ *                 are per image: the labels of image b do not carry b H W.
+ *   size          (int32, B x H x W) size_g = the number of pixels of g's component, 0 for an invalid pixel.
+ *   info          (int64, 3 B + 1 words) per image the number of components (pixels with label_g == g), the number of valid pixels and the largest
+ *                 component's size; then one status word, 0 when every loop of the kernels ran to its end.  Every data-dependent loop is cut after
+ *                 H W iterations, which a correct kernel never reaches, and then sets a bit there (1: tile pass, 2: border merge, 4: flatten) --
+ *                 the outputs of such a call mean nothing.
+ * Both outputs are written in full, the -1 / 0 of the invalid pixels included, and nothing beyond them.  The result is a function of the input alone:
+ * not of the launch geometry, the order in which workgroups arrive or falnet_set_deterministic; two calls give the same bits (integer atomics only:
+ * min, add, max).  workspace: falnet_components_workspace_bytes(B, H, W) bytes (0 for a refused shape), 8-byte aligned as info; map, score and the two
+ * outputs 4-byte aligned.  H = 1 or W = 1 is legal.  Refused with nothing launched: a NULL map, size, info or workspace, B < 1, H W < 1, H W >= 2^30,
+ * B H W >= 2^31, lo / hi outside the stated order (a NaN included), ratio < 1 or NaN, a misaligned pointer.  Four launches for a batch of up to 65535
+ * maps, the image index in the block index.  Not replayable. */
+int64_t falnet_components_workspace_bytes(int B, int H, int W);
+int falnet_components(const float* map, const float* score, float threshold, float lo, float hi, float ratio, int B, int H, int W, int32_t* label,
+                      int32_t* size, int64_t* info, void* workspace, void* stream);
+
 /* ---- stable segmented argsort (csrc/sort.hip; fal_net_amd/sparsification.py: argsort_u32) ---------------------------------------------------
  * keys: `segments` independent arrays of n u32 keys each, keys[s * n + i], 1 <= segments <= 8, n <= 2^24, on the device, never written.
  * perm[s * n + r] = the index i of the element of segment s that has rank r in ascending key order; equal keys stay in ascending index order
