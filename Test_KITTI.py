@@ -24,6 +24,8 @@ fal_net_amd/sparsification.py;
 `--mesh [--mesh-max-jump T ...]` adds each frame's depth as a triangle mesh Mesh/<frame>.ply, cut where depth jumps, fal_net_amd/mesh.py;
 `--min-component K [--component-jump T]` drops from the mesh and the scan the pixels in connected pieces of the disparity map smaller than K pixels,
 fal_net_amd/components.py;
+`--cloud-metrics [--cm-thresholds T1,T2,... --cm-on gt|all --cm-beams N --cm-max-depth M]` writes cloud_errors.txt: Chamfer distance and F-score
+between the back-projected prediction and ground truth, fal_net_amd/cloud_metrics.py;
 fal_net_amd/dumps.py: the images, feature maps and point-cloud records are finished by HIP kernels, the host only encodes files); the
 reference's `-save*` switches parse and are still refused when true.  `--dtype f16` is the recommended 16-bit
 inference type (depth abs_rel vs the f32 path 2e-3, bf16 1.7e-2, at the same speed)."""
@@ -350,6 +352,70 @@ def settings_hidden(a):
     return hidden_settings(a) + tuple(n for _, names, on, _ in LATER_FAMILIES if not on(a) for n in names)
 
 
+def _cm_thresholds(v):
+    from fal_net_amd.cloud_metrics import check_thresholds
+    try:
+        return list(check_thresholds([float(x) for x in v.split(',') if x]))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError('--cm-thresholds: {}'.format(e))
+
+
+parser.add_argument('--cloud-metrics', action='store_true',
+                    help='also score each frame in 3-D: the predicted depth back-projected into a point cloud against the back-projected ground truth -- '
+                         'accuracy, completeness and Chamfer distance in metres, precision / recall / F-score at --cm-thresholds -- by an all-pairs nearest-'
+                         'neighbour kernel on the device (fal_net_amd/cloud_metrics.py); writes cloud_errors.txt and one JSON line.  Dataset mode with '
+                         '-eval True only; the calibration is --pseudo-lidar\'s (--pl-calib, the frame\'s own, or a nominal camera)')
+parser.add_argument('--cm-thresholds', type=_cm_thresholds, default=None, metavar='T1,T2,...',
+                    help='--cloud-metrics: up to 8 increasing distance thresholds of the F-score in metres (default 0.1,0.25,0.5,1.0)')
+parser.add_argument('--cm-on', default='gt', choices=['gt', 'all'],
+                    help='--cloud-metrics: the predicted cloud holds only the pixels that carry ground truth (gt), or every pixel (all)')
+parser.add_argument('--cm-beams', type=_int_in('--cm-beams', 0, 128), default=0, metavar='N',
+                    help='--cloud-metrics: N > 0 first reduces the predicted cloud to the nearest point of each of N elevation x 1024 azimuth bins')
+parser.add_argument('--cm-max-depth', type=_positive('--cm-max-depth'), default=80.0, metavar='M', help='--cloud-metrics: points of either cloud beyond M metres are dropped')
+CLOUD_ARGS = ('cloud_metrics', 'cm_thresholds', 'cm_on', 'cm_beams', 'cm_max_depth')
+# Families added after settings_hidden() was pinned to the two tables above: the same four-tuples again, walked after LATER_FAMILIES by
+# check_family_args and by the settings.txt filter (settings_left_out)
+NEWER_FAMILIES = (
+    ('--cloud-metrics', CLOUD_ARGS, lambda a: a.cloud_metrics, True),
+)
+LATER_LINE_ORDER = ('cloud',)  # the JSON lines printed after LINE_ORDER's
+
+
+def settings_left_out(a):
+    """What settings.txt leaves out: settings_hidden, then the names of every newer family that is off."""
+    return settings_hidden(a) + tuple(n for _, names, on, _ in NEWER_FAMILIES if not on(a) for n in names)
+
+
+def check_cloud_args(a, dataset_mode):
+    """--cloud-metrics needs ground truth.  SystemExit says which."""
+    if not a.cloud_metrics:
+        return
+    if not dataset_mode:
+        raise SystemExit('--cloud-metrics compares the predicted cloud with the ground truth\'s, and synthetic mode has no ground truth: give a dataset (-d <root>)')
+    if not a.evaluate:
+        raise SystemExit('--cloud-metrics needs the ground truth: run with -eval True')
+
+
+def write_cloud_errors(path, res):
+    """cloud_errors.txt: the means over the counted frames, then one line per frame."""
+    K = range(len(res['thresholds']))
+    head = ['accuracy', 'completeness', 'chamfer', 'chamfer_l2'] + ['{}@{:g}'.format(k, t) for t in res['thresholds'] for k in ('P', 'R', 'F')]
+
+    def line(acc, comp, ch, ch2, P, R, F):
+        return ''.join('{:>14.6f}'.format(v) for v in [acc, comp, ch, ch2] + [x[k] for k in K for x in (P, R, F)])
+
+    with open(path, 'w') as f:
+        f.write('Cloud metrics over {} frames (distances in metres between the back-projected prediction and ground truth; accuracy: prediction -> '
+                'ground truth, completeness: ground truth -> prediction, chamfer: their sum, chamfer_l2: the same of the squared distances; '
+                'P / R / F at each threshold)\n'.format(res['frames']))
+        f.write('{:>8s}{:>10s}{:>10s}'.format('frame', 'n_pred', 'n_gt') + ''.join('{:>14s}'.format(h) for h in head) + '\n')
+        f.write('{:>8s}{:>10.1f}{:>10.1f}'.format('mean', res['n_pred_mean'], res['n_gt_mean']) + line(*(res[k + '_mean'] for k in (
+            'accuracy', 'completeness', 'chamfer', 'chamfer_l2', 'precision', 'recall', 'f'))) + '\n')
+        for i in range(len(res['rows'])):
+            f.write('{:>8d}{:>10.0f}{:>10.0f}'.format(i, res['n_pred'][i], res['n_gt'][i]) + line(*(res[k][i] for k in (
+                'accuracy', 'completeness', 'chamfer', 'chamfer_l2', 'precision', 'recall', 'f'))) + '\n')
+
+
 def check_component_args(a):
     """--min-component filters the products that have pixels to drop; SystemExit names them when neither is on."""
     if a.min_component is not None and not (a.mesh or a.pseudo_lidar):
@@ -359,7 +425,7 @@ def check_component_args(a):
 def check_family_args(a):
     """A family's parameters change nothing without its switch: SystemExit names the ones that were given (the families whose parameters are
     refused; --sweep-range and the --freeview path parameters are accepted in silence)."""
-    for switch, names, on, strict in FAMILIES + LATER_FAMILIES:
+    for switch, names, on, strict in FAMILIES + LATER_FAMILIES + NEWER_FAMILIES:
         given = [] if on(a) or not strict else [n for n in names[1:] if getattr(a, n) != parser.get_default(n)]
         if given:
             raise SystemExit('{} {} a parameter of {}: add {}'.format(', '.join('--' + n.replace('_', '-') for n in given),
@@ -467,17 +533,19 @@ LINE_ORDER = ('view', 'sparsification', 'pseudo_lidar', 'mesh', 'sweep', 'freevi
 def extra_lines(products):
     """One JSON line {key: summary()} per product that has a summary, with what the product wants beside its key."""
     lines = {p.key: dict({p.key: p.summary()}, **getattr(p, 'beside', {})) for p in products if hasattr(p, 'summary')}
-    for key in LINE_ORDER:
+    for key in LINE_ORDER + LATER_LINE_ORDER:
         if key in lines:
             print(json.dumps(lines[key]))
 
 
 def write_tables(save_path, results):
-    """view_errors.txt and sparsification.txt from the products' results, where the run has them."""
+    """view_errors.txt, sparsification.txt and cloud_errors.txt from the products' results, where the run has them."""
     if 'view' in results:
         write_view_errors(os.path.join(save_path, 'view_errors.txt'), results['view'])
     if 'sparsification' in results:
         write_sparsification(os.path.join(save_path, 'sparsification.txt'), results['sparsification'])
+    if 'cloud' in results:
+        write_cloud_errors(os.path.join(save_path, 'cloud_errors.txt'), results['cloud'])
 
 
 def main():
@@ -495,6 +563,7 @@ def main():
     check_component_args(args)
     dataset_mode = bool(args.data) and not args.synthetic
     check_sparsification_args(args, dataset_mode)
+    check_cloud_args(args, dataset_mode)
     model_dir = checkpoint_path(args)  # :119-120
     have_ckpt = os.path.isfile(model_dir)
     if args.checkpoint and not have_ckpt:
@@ -566,6 +635,15 @@ def main():
             from fal_net_amd import components
             jump = args.component_jump if args.component_jump is not None else (args.mesh_max_jump if args.mesh else 0.05)
             products.append(components.ComponentsSummary(args.min_component, jump))
+        if args.cloud_metrics:
+            from fal_net_amd import cloud_metrics
+            calibration, source = lidar_calibration(args, triples)
+            if source == 'nominal':
+                print('=> cloud metrics: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
+                      'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
+            products.append(cloud_metrics.CloudMetrics(n_frames, calibration, thresholds=args.cm_thresholds or cloud_metrics.THRESHOLDS, on=args.cm_on,
+                                                       beams=args.cm_beams, max_depth=args.cm_max_depth, device=dev,
+                                                       beside={'file': os.path.join(save_path, 'cloud_errors.txt'), 'calibration': source}))
         return products
 
     if dataset_mode:
@@ -584,7 +662,7 @@ def main():
         loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            hidden = settings_hidden(args)
+            hidden = settings_left_out(args)
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         products = make_products(triples)

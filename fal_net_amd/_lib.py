@@ -226,13 +226,19 @@ SIGNATURES = {
     "falnet_sort_u32": [_P, _L, _I, _P, _P, _P],
     "falnet_sparsify_workspace_bytes": [_I, _I, _I],
     "falnet_sparsify": [_P, _P, _I, _I, _I, _D, _P, _D, _D, Scores, _I, _P, _P, _P],
+    "falnet_nearest_splits": [_L, _L],
+    "falnet_nearest_workspace_bytes": [_L, _L, _I],
+    "falnet_nearest": [_P, _L, _P, _L, _I, _P, _P, _P, _P],
+    "falnet_cloud_errors_workspace_bytes": [],
+    "falnet_cloud_errors": [_P, _L, _P, _L, _P, _I, _P, _P, _P],
 }
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
              "falnet_lidar_workspace_bytes": C.c_int64, "falnet_sort_u32_workspace_bytes": C.c_int64,
              "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64,
              "falnet_inpaint_workspace_bytes": C.c_int64, "falnet_mesh_workspace_bytes": C.c_int64,
-             "falnet_components_workspace_bytes": C.c_int64}
+             "falnet_components_workspace_bytes": C.c_int64, "falnet_nearest_workspace_bytes": C.c_int64,
+             "falnet_cloud_errors_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

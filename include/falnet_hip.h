@@ -934,6 +934,48 @@ int64_t falnet_sparsify_workspace_bytes(int H, int W, int n_scores);
 int falnet_sparsify(const float* pred_disp, const float* gt, int H, int W, int mode, double fb, const double* scale, double min_d, double max_d,
                     falnet_scores_t scores, int steps, double* row, void* workspace, void* stream);
 
+/* ---- cloud metrics: nearest neighbour, Chamfer distance and F-score (csrc/nearest.hip; fal_net_amd/cloud_metrics.py) ---------------------------
+ * query: nq records, ref: nr records on the device; a record is 4 consecutive f32 x, y, z, . -- the 16-byte point of falnet_velo_unproject and of a
+ * KITTI .bin file; the fourth value is ignored.  0 <= nq, nr < 2^31.  For a query q and a reference r (the numpy restatement is
+ * tests/_cloud_ref.py):
+ *   dx = qx - rx, dy = qy - ry, dz = qz - rz;   d2(q, r) = (dx dx + dy dy) + dz dz
+ * every operation rounded to f32 in this order, no fused multiply-add.  A pair whose d2 is NaN -- a non-finite coordinate, inf - inf -- does not take
+ * part.  d2[q] (f32) is the minimum over the pairs that take part, idx[q] (int32) the smallest r that attains it; a query with no pair taking part
+ * (nr = 0 included) gets d2 = +inf, idx = -1.  nq = 0 issues no launch.  d2 is >= +0 or NaN, so its bits are monotone as an unsigned integer, and the
+ * 64-bit key (bits(d2) << 32) | r decides value and tie together: the result does not depend on how the references are divided among workgroups,
+ * and is bit-identical to the host restatement and from run to run.
+ * splits: into how many ranges of whole tiles the references are divided over the grid's second dimension; 0: falnet_nearest_splits(nq, nr), the
+ * library's choice (1 for an empty set, 0 for a refused shape); at most 1024.  One split stores the result plainly; S > 1 takes one integer atomicMin
+ * per query and split on a u64 key in `workspace` -- falnet_nearest_workspace_bytes(nq, nr, splits) bytes, 8-byte aligned, 0 bytes (and may be NULL)
+ * for one split; the library fills it on the stream, and a finishing launch unpacks it.  No floating-point atomics.  query and ref 16-byte aligned,
+ * d2 and idx 4-byte aligned.  Refused with nothing launched: a NULL pointer, nq or nr outside [0, 2^31), splits outside [0, 1024], a misaligned
+ * pointer.  Not replayable. */
+int falnet_nearest_splits(int64_t nq, int64_t nr);
+int64_t falnet_nearest_workspace_bytes(int64_t nq, int64_t nr, int splits);
+int falnet_nearest(const float* query, int64_t nq, const float* ref, int64_t nr, int splits, float* d2, int32_t* idx, void* workspace, void* stream);
+
+/* The sums of one frame's two d2 arrays -- prediction -> ground truth (n_pred entries) and ground truth -> prediction (n_gt entries), both on the
+ * device -- into one row of FALNET_CLOUD_ROW doubles of a device-resident table.  tau2: K <= FALNET_CLOUD_MAX_THRESHOLDS doubles on the HOST,
+ * tau2[k] = tau_k tau_k, each >= 0.  Per direction, over the FINITE entries only (a non-finite one is left out of everything):
+ *   n = their number;  sum sqrt((double)d2);  sum (double)d2;  per k < K the count of (double)d2 <= tau2[k]   (the counts of k >= K are 0)
+ * The sums are f64 over a fixed grid in a fixed order (a thread's stride, the shuffles of a wave, the waves, the workgroups): two calls give the same
+ * bits; the counts are exact.  Means and ratios (accuracy, completeness, Chamfer distance, precision, recall, F-score) are the host's to form after
+ * reading the table.  workspace: falnet_cloud_errors_workspace_bytes() bytes, 8-byte aligned as row; the d2 arrays 4-byte aligned (NULL with 0
+ * entries is legal).  Two launches.  Not replayable. */
+#define FALNET_CLOUD_MAX_THRESHOLDS 8
+#define FALNET_CLOUD_N_PRED 0      /* finite entries of the prediction -> ground truth array */
+#define FALNET_CLOUD_SUM_PRED 1    /* sum of their sqrt: metres */
+#define FALNET_CLOUD_SUMSQ_PRED 2  /* sum of them: square metres */
+#define FALNET_CLOUD_N_GT 3        /* the same three of the ground truth -> prediction array */
+#define FALNET_CLOUD_SUM_GT 4
+#define FALNET_CLOUD_SUMSQ_GT 5
+#define FALNET_CLOUD_HIT_PRED 6    /* 8 columns: prediction entries within tau_k (precision's numerator) */
+#define FALNET_CLOUD_HIT_GT 14     /* 8 columns: ground-truth entries within tau_k (recall's numerator) */
+#define FALNET_CLOUD_ROW 22
+int64_t falnet_cloud_errors_workspace_bytes(void);
+int falnet_cloud_errors(const float* d2_pred, int64_t n_pred, const float* d2_gt, int64_t n_gt, const double* tau2, int K, double* row,
+                        void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
