@@ -386,6 +386,73 @@ def settings_left_out(a):
     return settings_hidden(a) + tuple(n for _, names, on, _ in NEWER_FAMILIES if not on(a) for n in names)
 
 
+def _ground_arg(name, key, cast):
+    """argparse type of one --ground-* parameter: the range check is ground.check_fit_args's."""
+    def parse(v):
+        from fal_net_amd.ground import check_fit_args
+        try:
+            return check_fit_args(**{key: cast(v)})[key]
+        except ValueError as e:
+            raise argparse.ArgumentTypeError('{}: {}'.format(name, e))
+    return parse
+
+
+def _remove_ground(v):
+    x = float(v)
+    if not -float('inf') < x < float('inf'):
+        raise argparse.ArgumentTypeError('--pl-remove-ground needs a finite height in metres, got {}'.format(v))
+    return x
+
+
+parser.add_argument('--ground', action='store_true',
+                    help='also fit each frame\'s road plane: the depth back-projected densely (no height ceiling, within --pl-max-depth), plane hypotheses '
+                         'through seeded point triples scored by their inlier count in an all-pairs kernel on the device, the winner refitted from the '
+                         'moments of its inliers (fal_net_amd/ground.py); writes Ground/<frame>.txt in the KITTI-object planes format (camera axes) and one '
+                         'JSON line with the mean camera height, tilt, inlier fraction and rms; the calibration is --pseudo-lidar\'s')
+parser.add_argument('--ground-tol', type=_ground_arg('--ground-tol', 'tol', float), default=0.15, metavar='M',
+                    help='--ground / --pl-remove-ground: a point within M metres of a plane, vertically, is its inlier')
+parser.add_argument('--ground-hypotheses', type=_ground_arg('--ground-hypotheses', 'hypotheses', int), default=512, metavar='N',
+                    help='--ground / --pl-remove-ground: the number of plane hypotheses, 1 to 4096')
+parser.add_argument('--ground-seed', type=int, default=0, metavar='S', help='--ground / --pl-remove-ground: the seed of the hypotheses\' point triples')
+parser.add_argument('--ground-max-tilt', type=_ground_arg('--ground-max-tilt', 'max_tilt', float), default=15.0, metavar='DEG',
+                    help='--ground / --pl-remove-ground: hypotheses tilted more than DEG degrees against the sensor\'s horizontal are left out')
+parser.add_argument('--ground-refits', type=_ground_arg('--ground-refits', 'refits', int), default=2, metavar='K',
+                    help='--ground / --pl-remove-ground: the plane is refitted K >= 1 times from the moments of its inliers')
+parser.add_argument('--pl-remove-ground', type=_remove_ground, nargs='?', const=0.2, default=None, metavar='H',
+                    help='--pseudo-lidar: take the ground out of the scan -- every point at most H metres (0.2 when the switch is given alone) above the '
+                         'frame\'s fitted road plane is dropped; a frame without a plane is written unfiltered and counted')
+GROUND_ARGS = ('ground', 'ground_tol', 'ground_hypotheses', 'ground_seed', 'ground_max_tilt', 'ground_refits')
+REMOVE_GROUND_ARGS = ('pl_remove_ground',)
+# Families added after settings_left_out() was pinned to the three tables above: the same four-tuples once more, walked after NEWER_FAMILIES by
+# check_family_args and by the settings.txt filter (settings_omitted).  The --ground-* parameters belong to both switches.
+GROUND_FAMILIES = (
+    ('--ground', GROUND_ARGS, lambda a: a.ground or a.pl_remove_ground is not None, True),
+    ('--pl-remove-ground', REMOVE_GROUND_ARGS, lambda a: a.pl_remove_ground is not None, False),
+)
+GROUND_LINE_ORDER = ('ground',)  # the JSON lines printed after LATER_LINE_ORDER's
+
+
+def ground_left_out(a):
+    """The names of every ground family that is off: what settings.txt leaves out besides settings_left_out."""
+    return tuple(n for _, names, on, _ in GROUND_FAMILIES if not on(a) for n in names)
+
+
+def settings_omitted(a):
+    """Everything settings.txt leaves out: settings_left_out, then ground_left_out."""
+    return settings_left_out(a) + ground_left_out(a)
+
+
+def check_ground_args(a):
+    """--pl-remove-ground filters the scan of --pseudo-lidar.  SystemExit says so."""
+    if a.pl_remove_ground is not None and not a.pseudo_lidar:
+        raise SystemExit('--pl-remove-ground takes the ground out of the scan of --pseudo-lidar: add --pseudo-lidar')
+
+
+def ground_fit_args(a):
+    """The --ground-* parameters as the keywords of ground.fit."""
+    return dict(tol=a.ground_tol, hypotheses=a.ground_hypotheses, seed=a.ground_seed, max_tilt=a.ground_max_tilt, refits=a.ground_refits)
+
+
 def check_cloud_args(a, dataset_mode):
     """--cloud-metrics needs ground truth.  SystemExit says which."""
     if not a.cloud_metrics:
@@ -425,7 +492,7 @@ def check_component_args(a):
 def check_family_args(a):
     """A family's parameters change nothing without its switch: SystemExit names the ones that were given (the families whose parameters are
     refused; --sweep-range and the --freeview path parameters are accepted in silence)."""
-    for switch, names, on, strict in FAMILIES + LATER_FAMILIES + NEWER_FAMILIES:
+    for switch, names, on, strict in FAMILIES + LATER_FAMILIES + NEWER_FAMILIES + GROUND_FAMILIES:
         given = [] if on(a) or not strict else [n for n in names[1:] if getattr(a, n) != parser.get_default(n)]
         if given:
             raise SystemExit('{} {} a parameter of {}: add {}'.format(', '.join('--' + n.replace('_', '-') for n in given),
@@ -533,7 +600,7 @@ LINE_ORDER = ('view', 'sparsification', 'pseudo_lidar', 'mesh', 'sweep', 'freevi
 def extra_lines(products):
     """One JSON line {key: summary()} per product that has a summary, with what the product wants beside its key."""
     lines = {p.key: dict({p.key: p.summary()}, **getattr(p, 'beside', {})) for p in products if hasattr(p, 'summary')}
-    for key in LINE_ORDER + LATER_LINE_ORDER:
+    for key in LINE_ORDER + LATER_LINE_ORDER + GROUND_LINE_ORDER:
         if key in lines:
             print(json.dumps(lines[key]))
 
@@ -564,6 +631,7 @@ def main():
     dataset_mode = bool(args.data) and not args.synthetic
     check_sparsification_args(args, dataset_mode)
     check_cloud_args(args, dataset_mode)
+    check_ground_args(args)
     model_dir = checkpoint_path(args)  # :119-120
     have_ckpt = os.path.isfile(model_dir)
     if args.checkpoint and not have_ckpt:
@@ -623,6 +691,8 @@ def main():
                       'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
             products.append(pseudo_lidar.PseudoLidarWriter(save_path, calibration, beams=args.pl_beams, az_bins=args.pl_az_bins, max_depth=args.pl_max_depth,
                                                            max_height=args.pl_max_height, min_conf=args.pl_min_conf, extra={'calibration': source},
+                                                           **({} if args.pl_remove_ground is None else
+                                                              {'remove_ground': args.pl_remove_ground, 'ground': ground_fit_args(args)}),
                                                            **({} if args.min_component is None else
                                                               {'min_component': args.min_component,
                                                                'component_jump': 0.05 if args.component_jump is None else args.component_jump})))
@@ -644,6 +714,13 @@ def main():
             products.append(cloud_metrics.CloudMetrics(n_frames, calibration, thresholds=args.cm_thresholds or cloud_metrics.THRESHOLDS, on=args.cm_on,
                                                        beams=args.cm_beams, max_depth=args.cm_max_depth, device=dev,
                                                        beside={'file': os.path.join(save_path, 'cloud_errors.txt'), 'calibration': source}))
+        if args.ground:
+            from fal_net_amd import ground
+            calibration, source = lidar_calibration(args, triples)
+            if source == 'nominal':
+                print('=> ground: no calibration files (--pl-calib, or --velodyne-root on the original split): a nominal camera is used, the '
+                      'KITTI focal length and baseline for the image width, the principal point at the image centre, no translation')
+            products.append(ground.GroundPlanes(save_path, calibration, max_depth=args.pl_max_depth, extra={'calibration': source}, **ground_fit_args(args)))
         return products
 
     if dataset_mode:
@@ -662,7 +739,7 @@ def main():
         loader = DS.make_loader(dataset, 1, args.workers, shuffle=False, drop_last=False)  # B = 1: KITTI mixes sizes (:113)
         os.makedirs(save_path, exist_ok=True)
         with open(os.path.join(save_path, 'settings.txt'), 'w') as f:  # :63-75
-            hidden = settings_left_out(args)
+            hidden = settings_left_out(args) + ground_left_out(args)
             f.write(''.join('%15s: %s\n' % (k, v) for k, v in vars(args).items() if k not in hidden))
         print('=> {} test frames under {}; saving to {}'.format(len(triples), root, save_path))
         products = make_products(triples)

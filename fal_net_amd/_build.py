@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libfalnet_hip.so")
-SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_pose.hip", "inpaint.hip", "med_stats.hip", "compact.hip", "losses.hip", "adam.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "ssim.hip", "velo.hip", "lidar.hip", "mesh.hip", "components.hip", "sort.hip", "sparsify.hip", "nearest.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
+SOURCES = ["api.cpp", "replay.cpp", "med_head.hip", "med_head2.hip", "med_sweep.hip", "med_pose.hip", "inpaint.hip", "med_stats.hip", "compact.hip", "losses.hip", "adam.hip", "elementwise.hip", "data.hip", "augment_batch.hip", "dump.hip", "metrics.hip", "ssim.hip", "velo.hip", "lidar.hip", "mesh.hip", "components.hip", "sort.hip", "sparsify.hip", "nearest.hip", "ground.hip", "wgrad_rows.hip", "wgrad_wave.hip", "wgrad.hip", "pack.hip", "conv_wave.hip", "conv_dma.hip", "conv.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  The MED head kernels are f32 VALU work per pixel and plane: the SLP vectoriser pairs independent scalar
@@ -29,13 +29,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # even): contracted into a fused multiply-add, pixels cross a rounding boundary.  mesh.hip runs the point cloud's f32 vertex chain (csrc/pc_vertex.h,
 # whose includers all need the flag) and sums its normals in float64 in a fixed order: a vertex record and a kept triangle must be the host's bit for bit.
 # nearest.hip forms a pair's squared distance in f32 in a stated order (three differences, three products, two sums): contracted, a nearest distance
-# and the index that attains it would no longer be the host's bit for bit.
+# and the index that attains it would no longer be the host's bit for bit.  ground.hip forms a point's vertical residual to a plane in f32 and a
+# hypothesis plane in f64 in stated orders: contracted, an inlier count, a stored plane and a height would no longer be the host's bit for bit.
 FILE_FLAGS = {"med_head.hip": ["-fno-slp-vectorize"], "med_head2.hip": ["-fno-slp-vectorize"], "med_sweep.hip": ["-fno-slp-vectorize"],
               "med_stats.hip": ["-fno-slp-vectorize"], "med_pose.hip": ["-fno-slp-vectorize"],
               "dump.hip": ["-ffp-contract=off"],
               "metrics.hip": ["-ffp-contract=off"], "ssim.hip": ["-ffp-contract=off"], "augment_batch.hip": ["-ffp-contract=off"], "velo.hip": ["-ffp-contract=off"],
               "lidar.hip": ["-ffp-contract=off"], "sparsify.hip": ["-ffp-contract=off"], "mesh.hip": ["-ffp-contract=off"],
-              "nearest.hip": ["-ffp-contract=off"]}
+              "nearest.hip": ["-ffp-contract=off"], "ground.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out, deps):

@@ -231,6 +231,15 @@ SIGNATURES = {
     "falnet_nearest": [_P, _L, _P, _L, _I, _P, _P, _P, _P],
     "falnet_cloud_errors_workspace_bytes": [],
     "falnet_cloud_errors": [_P, _L, _P, _L, _P, _I, _P, _P, _P],
+    "falnet_ground_hypotheses": [_P, _L, _P, _L, _D, _P, _P],
+    "falnet_ground_splits": [_L, _L],
+    "falnet_ground_consensus_workspace_bytes": [_L, _L, _I],
+    "falnet_ground_consensus": [_P, _L, _P, _L, _F, _I, _P, _P, _P, _P],
+    "falnet_ground_moments_workspace_bytes": [],
+    "falnet_ground_moments": [_P, _L, _P, _F, _F, _F, _I, C.c_uint32, _F, _P, _P, _P],
+    "falnet_ground_heights": [_P, _L, _F, _F, _F, _F, _P, _P],
+    "falnet_ground_split_workspace_bytes": [_L],
+    "falnet_ground_split": [_P, _L, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P, _P, _P],
 }
 _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.c_int64, "falnet_percentile_workspace_bytes": C.c_int64,
              "falnet_metrics_workspace_bytes": C.c_int64, "falnet_compact_workspace_bytes": C.c_int64,
@@ -238,7 +247,8 @@ _RESTYPES = {"falnet_last_error": C.c_char_p, "falnet_wgrad_workspace_bytes": C.
              "falnet_sparsify_workspace_bytes": C.c_int64, "falnet_ssim_workspace_bytes": C.c_int64,
              "falnet_inpaint_workspace_bytes": C.c_int64, "falnet_mesh_workspace_bytes": C.c_int64,
              "falnet_components_workspace_bytes": C.c_int64, "falnet_nearest_workspace_bytes": C.c_int64,
-             "falnet_cloud_errors_workspace_bytes": C.c_int64}
+             "falnet_cloud_errors_workspace_bytes": C.c_int64, "falnet_ground_consensus_workspace_bytes": C.c_int64,
+             "falnet_ground_moments_workspace_bytes": C.c_int64, "falnet_ground_split_workspace_bytes": C.c_int64}
 
 _lib = None
 _TLS = threading.local()  # per-thread launch state: the pinned stream (stream_scope) and the active Recorder

@@ -6,7 +6,8 @@ sparsification.SparsificationTable (curves of the confidence scores against the 
 image), dumps.FrameWriter (the frame's outputs on disk), dumps.SweepWriter (views along the baseline), freeview.FreeviewWriter (free-viewpoint views),
 confidence.StatsWriter (statistics of the disparity distribution, the confidence-filtered point cloud), pseudo_lidar.PseudoLidarWriter (a
 Velodyne-format scan), mesh.MeshWriter (a triangle mesh cut at the depth edges), cloud_metrics.CloudMetrics (Chamfer distance and F-score between
-the back-projected prediction and ground truth) -- that is the order Test_KITTI.py lists them in.
+the back-projected prediction and ground truth), ground.GroundPlanes (the fitted road plane of the frame's scan) -- that is the order Test_KITTI.py
+lists them in.
 `evaluate(disparity="peak")` evaluates the peak disparity of the same forward instead of the expectation."""
 import math
 

@@ -123,12 +123,23 @@ class PseudoLidarWriter:
     so that a low-confidence pixel has size 0) become unproject's score with threshold K: only the pixels in components of at least K pixels are kept,
     and unproject sees only the size map.  An approximation: the components judge the bound on the disparity, unproject on its own f64 depth
     fb / disparity, so a pixel within rounding of a bound can count towards a size and still be dropped by unproject, or the reverse; and the scan's
-    x > 0 and max_height tests do not enter the graph -- a component is counted with the pixels those tests drop afterwards."""
+    x > 0 and max_height tests do not enter the graph -- a component is counted with the pixels those tests drop afterwards.
+    remove_ground = h: the ground is taken out of the scan.  The frame's plane is fitted (ground.fit with the parameters `ground`, a dict) on the
+    dense, ceiling-free unprojection of the frame (ground.dense_cloud: every pixel within max_depth, whatever the scan's own filters are), and the scan
+    that is written loses every point whose height above that plane (ground.heights) is <= h metres.  A frame without a plane is written unfiltered
+    and counted (summary: ground_failed).  None: the writer does exactly what it does without the parameter."""
     key = "pseudo_lidar"
 
     def __init__(self, save_path, calibration=None, beams=0, az_bins=1024, max_depth=80.0, max_height=1.0, min_conf=None, min_depth=0.0,
-                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0), extra=None, min_component=None, component_jump=0.05):
+                 elevation=(-24.8, 2.0), azimuth=(-45.0, 45.0), extra=None, min_component=None, component_jump=0.05, remove_ground=None, ground=None):
         from .components import check_jump, check_min_component
+        self.remove_ground, self.ground_kw = None, None
+        if remove_ground is not None:
+            from .ground import check_fit_args
+            self.remove_ground, self.ground_kw = float(remove_ground), check_fit_args(**dict(ground or {}))
+            if not np.isfinite(self.remove_ground):
+                raise ValueError("remove_ground must be a finite height in metres (or None), got {}".format(remove_ground))
+        self.ground_failed = self.ground_removed = 0
         if beams != 0:
             edge_tables(beams, az_bins, elevation, azimuth)  # the range checks, before the first frame
         check_min_conf(min_conf)
@@ -167,6 +178,15 @@ class PseudoLidarWriter:
                 score = score.reshape(disp.shape)
             score, threshold = components.size_score(disp, self.component_jump, lo=lo, hi=hi, score=score, threshold=threshold), float(self.min_component)
         pts = unproject(disp, P, fb=fb, score=score, threshold=threshold, **self.kw)
+        if self.remove_ground is not None:
+            from . import ground
+            plane = ground.fit(ground.dense_cloud(disp, P, fb, self.kw["max_depth"]), **self.ground_kw)
+            if plane is None:
+                self.ground_failed += 1
+            else:  # what is NOT in (-inf, h]: heights > h, and a NaN height
+                before = int(pts.shape[0])
+                pts = ground.split(pts, plane, float("-inf"), self.remove_ground, inside=False)
+                self.ground_removed += before - int(pts.shape[0])
         n = write_bin(self.file(i), pts)
         self.frames += 1
         self.points += n
@@ -183,4 +203,6 @@ class PseudoLidarWriter:
             out["min_conf"] = self.min_conf
         if self.min_component is not None:
             out["min_component"] = self.min_component
+        if self.remove_ground is not None:
+            out.update(remove_ground=self.remove_ground, ground_failed=self.ground_failed, ground_removed=self.ground_removed)
         return dict(out, **self.extra)

@@ -69,6 +69,27 @@ def nominal_matrix(H, W, focal):
     return np.hstack((np.dot(K, axes), np.zeros((3, 1))))
 
 
+def decompose(P):
+    """(K, R, t) of a 3 x 4 projection matrix P = K [R | t]: K upper triangular with a positive diagonal, R a rotation (det R = +1), by numpy's QR
+    of the reversed rows (an RQ decomposition) of M = P[:, :3], and t = K^-1 P[:, 3].  A matrix whose M has a negative determinant is the same
+    projection with the opposite sign: it is decomposed as -P.  nominal_matrix gives its own K and axes and t = 0."""
+    Pm = np.asarray(P, dtype=np.float64)
+    if Pm.shape != (3, 4):
+        raise ValueError("P: expected a 3 x 4 matrix, got shape {}".format(Pm.shape))
+    det = np.linalg.det(Pm[:, :3])
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError("decompose: the left 3 x 3 block of P is singular")
+    if det < 0.0:
+        Pm = -Pm
+    M = Pm[:, :3]
+    flip = np.eye(3)[::-1]
+    q, r = np.linalg.qr(np.dot(flip, M).T)  # flip M = r^T q^T  =>  M = (flip r^T flip) (flip q^T)
+    K, R = np.dot(flip, np.dot(r.T, flip)), np.dot(flip, q.T)
+    sign = np.diag(np.where(np.diag(K) < 0.0, -1.0, 1.0))  # K sign . sign R: the diagonal positive, the product unchanged
+    K, R = np.dot(K, sign), np.dot(sign, R)
+    return K, R, np.linalg.solve(K, Pm[:, 3])
+
+
 def focal_baseline(calib_dir, cam=2):
     """focal length times stereo baseline of the colour pair in calib_cam_to_cam.txt, f . |P_rect_02[0, 3] - P_rect_03[0, 3]| / f with f the focal
     length of camera `cam`: depth = focal_baseline / disparity for a disparity in pixels of that camera's image."""

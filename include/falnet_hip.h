@@ -976,6 +976,79 @@ int64_t falnet_cloud_errors_workspace_bytes(void);
 int falnet_cloud_errors(const float* d2_pred, int64_t n_pred, const float* d2_gt, int64_t n_gt, const double* tau2, int K, double* row,
                         void* workspace, void* stream);
 
+/* ---- the ground plane of a scan: consensus fit, moments, heights, removal (csrc/ground.hip; fal_net_amd/ground.py) -----------------------------
+ * points: n records on the device; a record is 4 consecutive f32 x, y, z, . -- the 16-byte point of falnet_velo_unproject (x forward, y left, z up);
+ * the fourth value is ignored.  A plane is held in height form z = p x + q y + r, and every residual is the vertical one (the numpy
+ * restatement is tests/_ground_ref.py):
+ *   e = z - ((p x + q y) + r)
+ * every operation rounded to f32 in this order, no fused multiply-add.  A point is an inlier of a plane iff |e| <= tol in f32; a NaN anywhere makes
+ * the comparison false, so a non-finite point never takes part.  The band is vertical on purpose: no square root is taken anywhere a result decides
+ * an integer; for the tilts admitted below it differs from the perpendicular band by less than 3.5 %.
+ *
+ * falnet_ground_hypotheses: triples is (H, 3) int32 on the device, indices into points.  Plane h is formed in f64 in this order, without FMA:
+ *   u = P1 - P0, v = P2 - P0;  nx = uy vz - uz vy, ny = uz vx - ux vz, nz = ux vy - uy vx;  p = -(nx / nz), q = -(ny / nz), r = z0 - (p x0 + q y0)
+ * It is valid iff p, q, r are finite and (p p + q q) <= tan2_max (a repeated index or a collinear triple gives nz = 0 and is invalid; so is an index
+ * outside [0, n), whose point is not read).  planes[h] = (f32 p, f32 q, f32 r, 1.0f), or four +0 when invalid.  f64 + - x / are IEEE on both sides:
+ * the host reproduces the planes bit for bit.  3 <= n < 2^31, 1 <= H <= FALNET_GROUND_MAX_HYPOTHESES.
+ *
+ * falnet_ground_consensus: counts[h] (u32) = the number of inliers of plane h, 0 for an invalid one.  best: FALNET_GROUND_BEST_WORDS 32-bit words,
+ * 8-byte aligned: the maximum of the 64-bit key (count << 32) | (0xffffffff - h) -- the largest count, ties to the smallest index -- as low and high
+ * word; the status (1: a plane; 0: no hypothesis has 3 inliers, "no plane"); the winning index (-1 without a plane); the bits of its f32 p, q, r
+ * (+0 without a plane); the largest count.  Counts are integers, so the result does not depend on how the points are divided among workgroups.
+ * splits: into how many ranges of whole tiles the points are divided over the grid's second dimension; 0: falnet_ground_splits(n, H), the library's
+ * choice (0 for a refused shape); at most 1024.  One split stores the counts plainly; S > 1 takes one integer atomicAdd per hypothesis and workgroup
+ * on the u32 counters of `workspace` -- falnet_ground_consensus_workspace_bytes(n, H, splits) bytes, 8-byte aligned, 0 bytes (and may be NULL) for
+ * one split; the library zeroes it on the stream.  No floating-point atomics.  Not replayable. */
+#define FALNET_GROUND_MAX_HYPOTHESES 4096
+#define FALNET_GROUND_BEST_WORDS 8
+#define FALNET_GROUND_BEST_KEY 0     /* two words: low, high */
+#define FALNET_GROUND_BEST_STATUS 2
+#define FALNET_GROUND_BEST_INDEX 3
+#define FALNET_GROUND_BEST_PLANE 4   /* three words: the bits of p, q, r */
+#define FALNET_GROUND_BEST_COUNT 7
+int falnet_ground_hypotheses(const float* points, int64_t n, const int32_t* triples, int64_t H, double tan2_max, float* planes, void* stream);
+int falnet_ground_splits(int64_t n, int64_t H);
+int64_t falnet_ground_consensus_workspace_bytes(int64_t n, int64_t H, int splits);
+int falnet_ground_consensus(const float* points, int64_t n, const float* planes, int64_t H, float tol, int splits, uint32_t* counts, uint32_t* best,
+                            void* workspace, void* stream);
+
+/* The moments of the inliers of one plane into one row of FALNET_GROUND_ROW doubles of a device-resident table: n, sum x, y, z, xx, xy, yy, xz, yz,
+ * zz in f64, products formed in f64 from the f32 coordinates, then the plane: index, count, p, q, r (the f32 values widened) and status.  The plane is
+ * the `best` record of falnet_ground_consensus in device memory -- no host round trip; status 0 sums nothing -- or, with best NULL, the caller's p, q,
+ * r, index and count (status 1).  The sums run over a fixed grid in a fixed order (a thread's stride, the shuffles of a wave, the waves, the
+ * workgroups): two calls give the same bits, n is exact.  workspace: falnet_ground_moments_workspace_bytes() bytes, 8-byte aligned as row.
+ * 3 <= n < 2^31.  Two launches.  Not replayable. */
+#define FALNET_GROUND_N 0
+#define FALNET_GROUND_SX 1
+#define FALNET_GROUND_SY 2
+#define FALNET_GROUND_SZ 3
+#define FALNET_GROUND_SXX 4
+#define FALNET_GROUND_SXY 5
+#define FALNET_GROUND_SYY 6
+#define FALNET_GROUND_SXZ 7
+#define FALNET_GROUND_SYZ 8
+#define FALNET_GROUND_SZZ 9
+#define FALNET_GROUND_INDEX 10   /* the winning hypothesis, -1 without one */
+#define FALNET_GROUND_COUNT 11   /* its inlier count */
+#define FALNET_GROUND_P 12       /* the plane whose inliers were summed */
+#define FALNET_GROUND_Q 13
+#define FALNET_GROUND_R 14
+#define FALNET_GROUND_STATUS 15  /* 1: a plane; 0: no plane, every sum is 0 */
+#define FALNET_GROUND_ROW 16
+int64_t falnet_ground_moments_workspace_bytes(void);
+int falnet_ground_moments(const float* points, int64_t n, const uint32_t* best, float p, float q, float r, int32_t index, uint32_t count, float tol,
+                          double* row, void* workspace, void* stream);
+
+/* heights[i] = (z - ((p x + q y) + r)) cz in the f32 chain above; cz = f32(1 / sqrt(1 + p p + q q)) of the refined plane is the host's to pass.
+ * falnet_ground_split keeps the records with lo < h <= hi (inside != 0) or every other record (inside == 0; a NaN height is outside every range), in
+ * point order -- the ordered compaction of csrc/ordered.h: count, one scan, scatter -- into out_points, at most `capacity` records; *count_dev (int64
+ * on the device) is the number kept, also when it exceeds the capacity, exactly as falnet_velo_unproject reports it.  workspace:
+ * falnet_ground_split_workspace_bytes(n) bytes, 8-byte aligned.  0 <= n < 2^31; n == 0 launches nothing and writes nothing.  Not replayable. */
+int falnet_ground_heights(const float* points, int64_t n, float p, float q, float r, float cz, float* heights, void* stream);
+int64_t falnet_ground_split_workspace_bytes(int64_t n);
+int falnet_ground_split(const float* points, int64_t n, float p, float q, float r, float cz, float lo, float hi, int inside, float* out_points,
+                        int64_t capacity, int64_t* count_dev, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
